@@ -9,13 +9,21 @@ preparation, 54 fused B-cos conv launches, head, arg-max, 54 layers of input-gra
 contribution maps -- followed (N > 1) by the single all-gather of per-rank logits and maps.  Inputs and
 weights are resident in HBM before the timed region.  Weak scaling: every rank processes its own 256 images.
 
-Besides the contract fields the JSON line carries
+A plain run sets up, warms up, times the K steps and prints the contract fields (metric, value, unit, higher_is_better,
+dtype, ms_per_step, step_times, config); `roofline` and `cpu_baseline` are null.  `--full` adds everything else the
+benchmark measures:
   roofline      fp32-MFMA roofline of the dominant kernel family (tapconv_kernel): algorithmic FLOP of the B-cos
                 contractions of one step (17.22 GFLOP/image) / the time spent in those launches,
                 measured live with HIP events on the launch stream inside the timed region (around every contraction
-                launch of every 20th timed step, which runs on ONE stream so that an event pair times its own launch only);
+                launch of every 20th timed step, which runs on ONE stream so that an event pair times its own launch only),
+                the shader clock / socket power sampled during the timed region, and the vendor GEMM / device copy beside it;
   cpu_baseline  the CPU oracle (the PyTorch-CPU restatement of the reference's path) timed on this host's cores on
-                a bounded sample (rank 0, N = 1 only).
+                a bounded sample (rank 0, N = 1 only);
+  gather_ms_per_step  (N > 1) the all-gather of one step by itself, outside the timed region.
+
+`--dump-outputs DIR` writes what the last timed step returned to its caller as DIR/<name>.npy (float32 / float64; integer
+outputs as float64, large outputs as a fixed seeded sample of their elements, 64 MB at most in all).  The inputs and weights
+are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -99,6 +107,12 @@ def parse():
     ap.add_argument("--no-kernel-events", action="store_true",
                     help="diagnostic: do not bracket the contraction launches with HIP events (roofline fields become null)")
     ap.add_argument("--no-telemetry", action="store_true", help="diagnostic: do not sample shader clock / socket power during the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: roofline (per-launch HIP events in every 20th timed step, "
+                         "clock / power telemetry, vendor GEMM and device-copy references), CPU baseline, (N > 1) the all-gather by itself")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step returned as DIR/<name>.npy (float32 / float64, a fixed "
+                         "seeded sample of large outputs, 64 MB at most in all)")
     ap.add_argument("--contraction", choices=("f16x2", "bf16x3", "f32"), default=None,
                     help="arithmetic of the contraction kernel (include/bcos_hip.h: bcos_set_contraction_mode); default: "
                          "the library default (f16x2 = row-scaled 2-way fp16 split, 3 products, fp32 accumulation)")
@@ -329,6 +343,37 @@ def vendor_gemm_reference(shapes, ours_ms, prod, n_ev, pipe_peak, dev):
                       "matrix for free --, no patch norms, no B-cos / BatchNorm / ReLU epilogue, no multiplier or maxima tensors)"))
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(outputs, dirname):
+    """--dump-outputs: every tensor of `outputs` (name -> tensor) as dirname/<name>.npy.  float64 stays float64, other floating
+    types become float32, integer / bool outputs float64 (exact).  An output larger than its share of the 64 MB budget is written
+    as a sample of its flattened elements at indices drawn from a generator seeded by its name and size, so that two runs with
+    the same arguments sample the same elements.  Returns name -> {shape, dtype, written elements} for the result line."""
+    import zlib
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    items = [(k, v) for k, v in outputs.items() if isinstance(v, torch.Tensor)]
+    share = DUMP_LIMIT_BYTES // max(len(items), 1)
+    info = {}
+    for name, t in items:
+        t = t.detach()
+        dt = torch.float64 if (t.dtype == torch.float64 or not t.is_floating_point()) else torch.float32
+        flat = t.reshape(-1)
+        n = flat.numel()
+        itemsize = 8 if dt == torch.float64 else 4
+        sampled = n * itemsize > share
+        if sampled:
+            rng = np.random.default_rng(zlib.crc32(f"{name}:{n}".encode()))
+            idx = np.sort(rng.integers(0, n, size=share // itemsize, dtype=np.int64))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        arr = flat.to(dt).cpu().numpy()
+        np.save(os.path.join(dirname, f"{name}.npy"), arr if sampled else arr.reshape(tuple(t.shape)))
+        info[name] = dict(shape=list(t.shape), dtype=str(t.dtype).replace("torch.", ""), written=int(arr.size), sampled=sampled)
+    return info
+
+
 def train_main(args):
     """`--train`: images/s of whole training steps of the B-cosified network on the HIP kernels -- through the engines' training plans
     (bcos_hip/train_plan.py, bcos_hip/vit_train_plan.py), or per layer on the nn.Module path (--no-train-plan).  One JSON line of the same shape as the metric's; the roofline prices the
@@ -375,6 +420,7 @@ def train_main(args):
     opt = torch.optim.SGD(params, lr=1e-4, momentum=0.9)
 
     path = {}
+    last = {}           # what the step hands its caller (--dump-outputs)
 
     def step():
         opt.zero_grad(set_to_none=True)
@@ -386,6 +432,7 @@ def train_main(args):
         if world > 1:
             bdist.allreduce_gradients(params)
         opt.step()
+        last.update(loss=loss.detach(), logits=logits.detach())
         return loss
 
     for _ in range(args.warmup):
@@ -438,6 +485,8 @@ def train_main(args):
                               "per-kernel time: the per-layer path is launch- and elementwise-bound at this batch size"),
         "cpu_baseline": None,
     }
+    if rank == 0 and args.dump_outputs:
+        result["outputs_dumped"] = dump_outputs(last, args.dump_outputs)
     if rank == 0:
         print(json.dumps(result), flush=True)
     if world > 1:
@@ -470,7 +519,7 @@ def main():
     # is power / clock limited under these kernels, so the roofline is also stated at the clock it actually sustained.  Started ahead
     # of the model build: the child has found its SMI source long before the timed region begins.
     sampler = None
-    if rank == 0 and not args.no_telemetry:
+    if rank == 0 and args.full and not args.no_telemetry:
         from bcos_hip import telemetry
         sampler = telemetry.Sampler(index=telemetry.physical_index(local_rank), interval=0.01).start()     # (SMI / sysfs count physical devices)
 
@@ -534,8 +583,9 @@ def main():
     if sampler is not None:
         sampler.wait_ready()
 
+    kernel_events = args.full and not args.no_kernel_events
     for w in range(args.warmup):
-        if w == 0 and not args.no_kernel_events and args.warmup > 1:
+        if w == 0 and kernel_events and args.warmup > 1:
             # the first warm-up step runs the way the event-carrying timed steps do (every launch on the caller's stream, over the whole
             # batch): the kernel instantiations, LDS / scratch reservations and arenas of THAT path are first-use costs too
             sub = getattr(eng, "subbatch_streams", 1)
@@ -553,7 +603,7 @@ def main():
     # HIP events on the launch stream around every contraction launch of a SAMPLE of the timed steps (every 20th: the
     # two events per launch cost ~7 us of stream time each, 0.9 ms per step if taken on every step)
     EVENT_STRIDE = 20
-    event_steps = [] if args.no_kernel_events else [i for i in range(args.steps) if i % EVENT_STRIDE == 0]
+    event_steps = [i for i in range(args.steps) if i % EVENT_STRIDE == 0] if kernel_events else []
     events = []
     # one HIP event per step boundary on the caller's stream (the engine's side streams are joined into it at the end of every
     # pass): per-step times -> median / min, and the two execution modes of the timed region reported apart
@@ -568,12 +618,12 @@ def main():
             ops.KERNEL_TIMING = []
             sub = getattr(eng, "subbatch_streams", 1)
             eng.subbatch_streams = 1
-            step(eager=True)
+            out = step(eager=True)
             eng.subbatch_streams = sub
             events += ops.KERNEL_TIMING
             ops.KERNEL_TIMING = None
         else:
-            step()
+            out = step()
         marks[i + 1].record()
     if pipe is not None:
         gathered = pipe.flush()             # the last exchanges complete inside the timed region
@@ -591,8 +641,11 @@ def main():
 
     # the collective by itself, outside the timed region: the packed all-gather of one step's results issued and waited for with nothing
     # to overlap it (inside the timed region it runs on RCCL's stream beside the next step's compute)
+    if args.dump_outputs and rank == 0:
+        # (no further step may run before the dump: the engine's output buffers can be reused by the next pass)
+        dumped = dump_outputs(out, args.dump_outputs)
     gather_ms = gather_bytes = None
-    if world > 1:
+    if world > 1 and args.full:
         out = step()
         payload = {k: out[k] for k in (("logits",) if args.forward_only else ("logits", "contribution_map"))}
         gather_bytes = int(sum(v.numel() * v.element_size() for v in payload.values()))
@@ -701,7 +754,7 @@ def main():
     # What the vendor's GEMM reaches on the same pipe at the same shapes: every matrix-bound launch of the step as ONE plain fp16 GEMM
     # (torch.matmul -> hipBLASLt / rocBLAS, fp32 accumulate) of the launch's M and N and `prod` x its K -- the matrix work the
     # split-f16 loop executes, without the split, the patch gather, the B-cos epilogue or any tensor beyond C.  Outside the timed region.
-    if rank == 0 and world == 1 and prod > 1 and not args.no_vendor_ref and mfma_shapes:
+    if rank == 0 and world == 1 and args.full and prod > 1 and not args.no_vendor_ref and mfma_shapes:
         try:
             roofline["by_bound"]["mfma"]["vendor_f16_gemm"] = vendor_gemm_reference(mfma_shapes, [m for m, _, _ in mfma], prod, n_ev, pipe_peak, dev)
         except Exception as exc:           # (an allocation failure of the reference must not cost the bench line)
@@ -710,7 +763,7 @@ def main():
     # copy kernel (bcos_stream_copy: eight global_load_dwordx4 in flight per thread, non-temporal; the microarchitecture guide measures
     # 6.29 TB/s for such a kernel) on 1 GiB -> 1 GiB of fp32, read + written bytes / time, outside the timed region.  torch's
     # dst.copy_(src) on the same buffers is reported beside it (the reference of round 5: ~5.0 TB/s, a fifth below).
-    if rank == 0 and world == 1 and not args.no_vendor_ref and hbm:
+    if rank == 0 and world == 1 and args.full and not args.no_vendor_ref and hbm:
         try:
             src = torch.empty(1 << 28, device=dev, dtype=torch.float32).normal_()
             dst = torch.empty_like(src)
@@ -785,9 +838,11 @@ def main():
                    "collective": "one packed async all_gather(logits, contribution maps) per step, double buffered" if world > 1 else "none",
                    # the all-gather alone (median of 5 issued with nothing beside them, max over ranks) and what every rank contributes
                    "gather_ms_per_step": gather_ms, "gather_bytes_per_rank": gather_bytes},
-        "roofline": roofline,
+        "roofline": roofline if args.full else None,      # (a plain run carries no per-launch events: nothing to price)
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and spec["family"] != "clip" and not args.forward_only:
+    if args.dump_outputs and rank == 0:
+        result["outputs_dumped"] = dumped
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and spec["family"] != "clip" and not args.forward_only:
         result["cpu_baseline"] = cpu_baseline(net, args.arch, args.cpu_sample)
     elif rank == 0:
         result["cpu_baseline"] = None

@@ -9,9 +9,9 @@ OUT=$ROOT/gpurun_out/prof_$TAG
 SUM=$ROOT/gpurun_out/profiles_$TAG
 mkdir -p "$OUT" "$SUM"
 export TMPDIR=/tmp
-ARGS="--steps 2 --warmup 1 --no-cpu-baseline --no-vendor-ref"
-# 1. the headline command as the driver runs it (CPU baseline included)
-python3 bench.py --steps 20 --warmup 5 > "$SUM/${TAG}_bench.json" 2> "$OUT/bench.err"
+ARGS="--full --steps 2 --warmup 1 --no-cpu-baseline --no-vendor-ref"
+# 1. the headline command with every figure the benchmark measures (roofline, CPU baseline included)
+python3 bench.py --full --steps 20 --warmup 5 > "$SUM/${TAG}_bench.json" 2> "$OUT/bench.err"
 # 2. kernel stats + HBM counters of the same workload (counters in their own passes, MI355X_MICROARCH.md).  The profiled runs keep
 #    every launch on ONE stream (BCOS_SUBBATCH_STREAMS=1: 116 contraction launches per step, each over the whole batch) -- the form
 #    bench.py's own event-carrying steps use -- so that a launch in the trace is the launch bench.py's HIP events bracket; with the
@@ -30,7 +30,7 @@ BCOS_SUBBATCH_STREAMS=1 LAYERS_CSV="$SUM/${TAG}_layers.csv" python3 scripts/laye
 # 4. the other BASELINE.json configurations: bench line + kernel stats each
 for spec in "resnet50 --forward-only" "resnet18" "vit_ti --batch 512" "vit_ti --batch 512 --forward-only" "clip_rn50" "clip_rn50 --forward-only"; do
   name=$(echo $spec | tr -d '-' | tr ' ' '_')
-  python3 bench.py --arch $spec --steps 10 --warmup 3 --no-cpu-baseline > "$SUM/${TAG}_bench_${name}.json" 2> "$OUT/bench_${name}.err"
+  python3 bench.py --full --arch $spec --steps 10 --warmup 3 --no-cpu-baseline > "$SUM/${TAG}_bench_${name}.json" 2> "$OUT/bench_${name}.err"
   cd /tmp
   rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats_${name}" -- python3 "$ROOT/bench.py" --arch $spec $ARGS > /dev/null 2> "$OUT/stats_${name}.err"
   cd "$ROOT"

@@ -1654,9 +1654,40 @@ def test_telemetry_sampler_and_bench_thread_pinning(tmp_path):
     probe = ("import sys, os; sys.argv = ['bench.py'] + {args!r}; os.environ.pop('OMP_PROC_BIND', None); os.environ.pop('WORLD_SIZE', None); "
              "src = open(os.path.join({repo!r}, 'bench.py')).read(); head = src[:src.index('import torch  # noqa')]; "
              "exec(compile(head, 'bench_head', 'exec'), dict(__file__=os.path.join({repo!r}, 'bench.py'), __name__='bench_head')); print(os.environ.get('OMP_PROC_BIND'), os.environ.get('OMP_PLACES'))")
-    for args, want in (([], "close cores"), (["--gpus", "8"], "None None"), (["--no-cpu-baseline"], "None None"), (["--train"], "None None")):
+    for args, want in (([], "close cores"), (["--full"], "close cores"), (["--gpus", "8"], "None None"), (["--no-cpu-baseline"], "None None"),
+                       (["--train"], "None None")):
         out = subprocess.run([sys.executable, "-c", probe.format(args=args, repo=repo)], capture_output=True, text=True, timeout=60)
         assert out.stdout.strip() == want, (args, out.stdout, out.stderr[-300:])
+
+
+def test_bench_dump_outputs_formats_and_samples(tmp_path):
+    """bench.py --dump-outputs: every output as <name>.npy in float32 / float64 (integer outputs exact in float64), small outputs whole,
+    a large one as a sample of its elements that is the same from run to run, 64 MB at most in all."""
+    import importlib.util
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(repo, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    g = torch.Generator().manual_seed(5)
+    big = torch.randn(5, 6, 1024, 1024, generator=g)                        # 120 MB of float32
+    outs = dict(logits=torch.randn(4, 10, generator=g), prediction=torch.tensor([3, 1, 2 ** 40, 0]),
+                scores=torch.randn(7, generator=g, dtype=torch.float64), half=torch.randn(3, 3, generator=g).half(), big=big)
+    info = [bench.dump_outputs(outs, str(tmp_path / d)) for d in ("a", "b")]
+    assert info[0] == info[1]
+    files = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert files == ["big.npy", "half.npy", "logits.npy", "prediction.npy", "scores.npy"]
+    a = {f[:-4]: np.load(tmp_path / "a" / f) for f in files}
+    b = {f[:-4]: np.load(tmp_path / "b" / f) for f in files}
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    assert sum((tmp_path / "a" / f).stat().st_size for f in files) <= 64 << 20
+    assert a["logits"].dtype == np.float32 and np.array_equal(a["logits"], outs["logits"].numpy())
+    assert a["scores"].dtype == np.float64 and np.array_equal(a["scores"], outs["scores"].numpy())
+    assert a["prediction"].dtype == np.float64 and a["prediction"].tolist() == [3.0, 1.0, 2.0 ** 40, 0.0]
+    assert a["half"].dtype == np.float32 and np.array_equal(a["half"], outs["half"].float().numpy())
+    assert info[0]["big"]["sampled"] and not info[0]["logits"]["sampled"] and info[0]["big"]["shape"] == [5, 6, 1024, 1024]
+    vals = a["big"]
+    assert vals.dtype == np.float32 and vals.ndim == 1 and 0 < vals.size == info[0]["big"]["written"] < big.numel()
+    assert np.isin(vals[:1000], big.numpy().reshape(-1)).all()              # elements of the output, not a reduction of it
 
 
 def test_training_pass_helpers_are_thread_local_and_bump_allocated():
