@@ -19,7 +19,7 @@ LIB_PATH = Path(os.environ["BCOS_HIP_LIB"]) if os.environ.get("BCOS_HIP_LIB") el
 CSRC = PKG_ROOT / "csrc"
 INCLUDE = REPO_ROOT / "include"
 SOURCES = ["bcos_tapconv.hip", "bcos_skinny.hip", "bcos_elementwise.hip", "bcos_vit.hip", "bcos_render.hip", "bcos_train.hip",
-           "bcos_abi.hip"]
+           "bcos_agc.hip", "bcos_abi.hip"]
 
 BCOS_NONE, BCOS_CONV_EPS, BCOS_LINEAR_EPS = 0, 1, 2
 BCOS_EPI_NORM_ONLY = 1
@@ -29,7 +29,7 @@ BCOS_EPI_GATE2_FROM_MUL = 8
 BCOS_EPI_MUL_FROM_ACT = 16
 BCOS_EPI_UNIT_NORM_W = 32
 BCOS_E_NOSUP = -95
-ABI_VERSION = 9
+ABI_VERSION = 10
 VERSION_DEV_FLAG = 0x40000000          # include/bcos_hip.h: BCOS_VERSION_DEV_FLAG
 TAPCONV_PARTS = 11
 
@@ -67,6 +67,11 @@ class Operands(C.Structure):
     _fields_ = [("a", C.c_void_p), ("a_absmax", C.c_void_p), ("wt", C.c_void_p), ("wt_bf16x3", C.c_void_p),
                 ("wt_f16x2", C.c_void_p), ("contraction", C.c_int32), ("a_imgmax", C.c_void_p), ("a_imgmin", C.c_void_p),
                 ("a_imgmin_c", C.c_void_p)]
+
+
+class AgcTensor(C.Structure):
+    """include/bcos_hip.h: bcos_agc_tensor"""
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("units", C.c_int64), ("unit_len", C.c_int64)]
 
 
 CONTRACT_DEFAULT, CONTRACT_F32, CONTRACT_BF16X3, CONTRACT_F16X2 = 0, 1, 2, 3
@@ -158,6 +163,7 @@ SIGNATURES = {
     "bcos_render_explanations": (C.c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _P]),
     "bcos_box_filter": (C.c_int, [_P, _P, _I, _I, _I, _I, _P]),
     "bcos_localisation_fractions": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "bcos_agc_clip": (C.c_int, [C.POINTER(AgcTensor), _I, _F, _F, _P]),
 }
 
 _lib = None

@@ -4,6 +4,7 @@ All activation tensors here are *physically* NHWC float32 HIP tensors of shape [
 (i.e. `x_nchw_channels_last.permute(0,2,3,1)`), weights are [Cout,kh,kw,Cin].
 """
 import ctypes as C
+import math
 from typing import Optional
 
 import os
@@ -1103,6 +1104,73 @@ def stream_copy(src: torch.Tensor, dst: torch.Tensor = None) -> torch.Tensor:
         raise BcosHipError("stream_copy: contiguous fp32 tensors of equal size")
     _l.check(_l.load().bcos_stream_copy(_dev(src, "src"), _dev(dst, "dst"), src.numel(), _stream()), "bcos_stream_copy")
     return dst
+
+
+_AGC_UNITS = {}          # shape -> (units, unit_len): agc_units of the shapes seen so far
+
+
+def agc_units(shape, name: str = "parameter"):
+    """(units, unit_len) of a parameter of `shape` for bcos_agc_clip: the units over which the reference's unitwise_norm
+    (bcos/training/agc.py:12-25) reduces.  A tensor whose squeeze() keeps at most one dimension is ONE unit (0-d scales, 1-D norm
+    weights, but also [64, 1, 1, 1], [1, 192] and [192, 1]); otherwise an OIHW tensor has one unit per output filter and a matrix one
+    per row.  A 3-D tensor reduces over its middle dimension -- strided units, which the device path does not take (BcosHipError naming
+    `name`); more than four dimensions is the reference's ValueError."""
+    shape = tuple(int(s) for s in shape)
+    numel = math.prod(shape)
+    if sum(s != 1 for s in shape) <= 1:
+        return 1, numel
+    if len(shape) == 4:
+        return shape[0], numel // shape[0]
+    if len(shape) == 2:
+        return shape[0], shape[1]
+    if len(shape) == 3:
+        raise BcosHipError(f"agc_clip: {name} has the 3-D shape {list(shape)}; its units (dim 1) are strided, which bcos_agc_clip does not "
+                           "take (bcos.training.agc.unitwise_norm computes their norms in torch)")
+    raise ValueError(f"Expected 1 <= x.ndim <= 4. Got x.ndim={len(shape)} ({name}: {list(shape)})")
+
+
+def _agc_refuse(name, p, g):
+    for t, what in ((p, "data"), (g, "grad")):
+        _dev(t, f"agc_clip: {name} ({what})")
+    if g.shape != p.shape or g.device != p.device:
+        raise BcosHipError(f"agc_clip: {name}: gradient {list(g.shape)} on {g.device} for a parameter {list(p.shape)} on {p.device}")
+
+
+def agc_clip(params, clip_factor: float = 0.01, eps: float = 1e-3):
+    """adaptive_clip_grad_ (bcos/training/agc.py:28-42, norm_type 2) of every parameter in `params` that has a gradient, in place, in ONE
+    call of bcos_agc_clip on the current stream (include/bcos_hip.h; one launch per 64 tensors).  `params`: tensors, or (name, tensor)
+    pairs for error messages that name the parameter.  Parameters and gradients must be contiguous fp32 HIP tensors on one device; the
+    gradients' version counters are bumped as the reference's copy_ would."""
+    descs, grads, seen, device = [], [], set(), None
+    for i, p in enumerate(params):
+        name, p = p if isinstance(p, tuple) else (f"parameter {i}", p)
+        g = p.grad
+        if g is None:
+            continue
+        if not (p.is_cuda and g.is_cuda and p.dtype is torch.float32 and g.dtype is torch.float32 and p.is_contiguous() and g.is_contiguous()
+                and g.shape == p.shape and g.device == p.device):
+            _agc_refuse(name, p, g)
+        if device is None:
+            device = g.device
+        elif g.device != device:
+            raise BcosHipError(f"agc_clip: {name} is on {g.device}, the parameters before it on {device}")
+        if g.numel() == 0:
+            continue
+        units = _AGC_UNITS.get(p.shape)
+        if units is None:
+            units = _AGC_UNITS[p.shape] = agc_units(p.shape, name)
+        gp = g.data_ptr()
+        if gp in seen:
+            raise BcosHipError(f"agc_clip: {name}: the same gradient appears twice in the list")
+        seen.add(gp)
+        descs.append((p.data_ptr(), gp) + units)
+        grads.append(g)
+    if not descs:
+        return
+    arr = (_l.AgcTensor * len(descs))(*descs)
+    stream = C.c_void_p(_RAW_STREAM(device.index)) if _RAW_STREAM is not None else C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    _l.check(_l.load().bcos_agc_clip(arr, len(descs), float(clip_factor), float(eps), stream), "bcos_agc_clip")
+    torch.autograd.graph.increment_version(grads)
 
 
 def check_targets(targets, n_logits: int, what: str = "targets"):

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define BCOS_ABI_VERSION 9
+#define BCOS_ABI_VERSION 10
 
 enum {
     BCOS_OK = 0,
@@ -782,6 +782,26 @@ int bcos_box_filter(const float* in, float* out, int N, int H, int W, int k, voi
  * positive, else 0; cell order as the reference's permute(0,1,3,2).reshape: index = col * rows + row. */
 int bcos_localisation_fractions(const float* attr, float* frac, int T, int H, int W, int cell_h, int cell_w, int neg,
                                 void* stream);
+
+/* -- training recipe: adaptive gradient clipping (ABI v10) ------------------------------------------------------------- */
+/* One (parameter, gradient) pair of bcos_agc_clip: `units` contiguous units of `unit_len` floats each, p and g laid out alike. */
+typedef struct bcos_agc_tensor {
+    const float* p;
+    float* g;
+    int64_t units;
+    int64_t unit_len;
+} bcos_agc_tensor;
+
+/* adaptive_clip_grad_ (bcos/training/agc.py:28-42, norm_type 2) of a whole parameter list, gradients rewritten in place.  Per unit u,
+ * in fp32: pn = ||p_u||_2, gn = ||g_u||_2, max_norm = clamp(pn, min=eps) * clip_factor; unless gn < max_norm,
+ * g_u <- g_u * (max_norm / clamp(gn, min=1e-6)) -- torch's clamp, which keeps a NaN, so a NaN norm clips the unit to NaN as the
+ * reference's torch.where does; units that do not clip are not written.  The caller chooses the units (unitwise_norm, agc.py:12-25):
+ * one unit for a tensor whose squeeze() has at most one dimension, one per output filter of an OIHW tensor, one per row of a matrix.
+ * `tensors` is a HOST array read during the call: the descriptors travel by value in the kernel arguments, 64 tensors per launch, so
+ * nothing is copied to the device, allocated or synchronised.  Fixed summation order, no atomics: two calls on the same data give the
+ * same bits.  BCOS_E_INVAL (before anything is launched) for a NULL array or pointer, ntensors <= 0, units or unit_len <= 0, an
+ * overflowing units * unit_len, or a clip_factor / eps that is not finite and positive. */
+int bcos_agc_clip(const bcos_agc_tensor* tensors, int ntensors, float clip_factor, float eps, void* stream);
 
 #ifdef __cplusplus
 }
