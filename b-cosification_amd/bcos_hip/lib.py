@@ -29,7 +29,7 @@ BCOS_EPI_GATE2_FROM_MUL = 8
 BCOS_EPI_MUL_FROM_ACT = 16
 BCOS_EPI_UNIT_NORM_W = 32
 BCOS_E_NOSUP = -95
-ABI_VERSION = 10
+ABI_VERSION = 11
 VERSION_DEV_FLAG = 0x40000000          # include/bcos_hip.h: BCOS_VERSION_DEV_FLAG
 TAPCONV_PARTS = 11
 
@@ -74,6 +74,13 @@ class AgcTensor(C.Structure):
     _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("units", C.c_int64), ("unit_len", C.c_int64)]
 
 
+class TapconvRoute(C.Structure):
+    """include/bcos_hip.h: bcos_tapconv_route"""
+    _fields_ = [(n, C.c_int32) for n in ("route", "epi_kind", "norm", "loop", "bm", "bn", "chunks", "ch_pass")]
+
+
+LOOP_NAMES = ("f32", "bf16x3", "bf16x3_presplit", "f16x2_regs", "f16x2_dma", "f16x2_patch")      # include/bcos_hip.h: BCOS_LOOP_*
+
 CONTRACT_DEFAULT, CONTRACT_F32, CONTRACT_BF16X3, CONTRACT_F16X2 = 0, 1, 2, 3
 
 # name -> (restype, argtypes); mirrors include/bcos_hip.h one to one
@@ -88,6 +95,10 @@ SIGNATURES = {
     "bcos_tapconv": (C.c_int, [_P, _P, C.POINTER(TapconvGeom), C.POINTER(Epilogue), _P]),
     "bcos_tapconv_ops": (C.c_int, [C.POINTER(Operands), C.POINTER(TapconvGeom), C.POINTER(Epilogue), _P]),
     "bcos_tapconv_fuses_image_range": (C.c_int, [C.POINTER(Operands), C.POINTER(TapconvGeom), C.POINTER(Epilogue)]),
+    "bcos_tapconv_route_query": (C.c_int, [C.POINTER(Operands), C.POINTER(TapconvGeom), C.POINTER(Epilogue), C.POINTER(TapconvRoute)]),
+    "bcos_tapconv_route_name": (C.c_char_p, [_I]),
+    "bcos_tapconv_route_count": (C.c_int, []),
+    "bcos_tapconv_epilogue_kinds": (C.c_int, []),
     "bcos_image_absmax": (C.c_int, [_P, _P, _I, _I, _P]),
     "bcos_image_absrange": (C.c_int, [_P, _P, _P, _I, _I, _P]),
     "bcos_image_absrange_c": (C.c_int, [_P, _P, _P, _I, _I, _P]),
@@ -283,6 +294,20 @@ def get_option(name: str) -> int:
     out = C.c_int64(0)
     check(load().bcos_get_option(OPTIONS[name], C.byref(out)), f"bcos_get_option({name})")
     return out.value
+
+
+def route_query(ops, geom, epi):
+    """What bcos_tapconv_ops(ops, geom, epi) would run: a dict with the route's name, epilogue kind, loop name, tile and chunk count
+    (bcos_tapconv_route_query; nothing is launched, no device is needed).  Raises BcosHipError where the launch would be rejected."""
+    r = TapconvRoute()
+    check(load().bcos_tapconv_route_query(C.byref(ops), C.byref(geom), C.byref(epi), C.byref(r)), "bcos_tapconv_route_query")
+    return {"route": load().bcos_tapconv_route_name(r.route).decode(), "epi_kind": r.epi_kind, "norm": r.norm, "loop": LOOP_NAMES[r.loop],
+            "bm": r.bm, "bn": r.bn, "chunks": r.chunks, "ch_pass": r.ch_pass}
+
+
+def route_names():
+    lib = load()
+    return [lib.bcos_tapconv_route_name(i).decode() for i in range(lib.bcos_tapconv_route_count())]
 
 
 class option:

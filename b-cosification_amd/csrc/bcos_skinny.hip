@@ -354,7 +354,7 @@ __global__ __launch_bounds__(SK_THREADS) void skinny_group_kernel(const SkGroupA
 
 // Returns 1 if the launch was handled here, 0 if the caller should use the generic kernel, < 0 on error.
 int bcos_try_skinny(const float* a, const float* wt, const bcos_tapconv_geom& g, const bcos_epilogue& e, int M,
-                    hipStream_t stream) {
+                    hipStream_t stream, int* decide_ch) {
     (void)M;
     if (g.Cout > 8) return 0;
     if (e.bcos_mode != BCOS_NONE || e.bias || e.ch_scale || e.ch_shift || e.relu || e.out2 || e.scale_out ||
@@ -385,6 +385,7 @@ int bcos_try_skinny(const float* a, const float* wt, const bcos_tapconv_geom& g,
     p.ldp = p.CH + 4;
     const int64_t blocks = (int64_t)g.N * p.tiles_i * p.tiles_j;
     if (blocks >= ((int64_t)1 << 31)) return 0;
+    if (decide_ch) { *decide_ch = p.CH; return 1; }
     static std::atomic<size_t> lds_hw{0};
     hipError_t err = bcos_ensure_dynamic_lds(reinterpret_cast<const void*>(skinny_kernel), lds, lds_hw);
     if (err != hipSuccess) return bcos_set_hip_error("hipFuncSetAttribute(skinny)", err);

@@ -3182,6 +3182,11 @@ constexpr size_t epilogue_lds() {
     return (size_t)SBM * (SBN + 4) * sizeof(float) + (size_t)BM * 20 + (size_t)BN * 4 + (size_t)BM * 8 + 144;      // (+ the row maxima of the column parts + the per-image range cells)
 }
 
+// which loop a launch_cfg launch instantiates -- the LOOP template argument of its kernel, numbered like BCOS_LOOP_F32 / BCOS_LOOP_BF16X3 /
+// BCOS_LOOP_BF16X3_PRESPLIT of include/bcos_hip.h: the one place that decides it, for the launch and for bcos_tapconv_route_query
+inline int cfg_loop(const KArgs& p) { return p.x3 ? (p.wt3 ? BCOS_LOOP_BF16X3_PRESPLIT : BCOS_LOOP_BF16X3) : BCOS_LOOP_F32; }
+static_assert(BCOS_LOOP_F32 == 0 && BCOS_LOOP_BF16X3 == 1 && BCOS_LOOP_BF16X3_PRESPLIT == 2, "cfg_loop returns the kernel's LOOP argument");
+
 template <int BM, int BN, int WAVES_M, int WAVES_N>
 int launch_cfg(const KArgs& base, bool norm, hipStream_t stream) {
     KArgs p = base;
@@ -3201,10 +3206,11 @@ int launch_cfg(const KArgs& base, bool norm, hipStream_t stream) {
         hipLaunchKernelGGL(k, grid, block, lds, stream, p);
         return hipSuccess;
     };
-    if (p.x3 && p.wt3) err = norm ? launch(tapconv_kernel<BM, BN, WAVES_M, WAVES_N, true, 2>, 0)
-                                  : launch(tapconv_kernel<BM, BN, WAVES_M, WAVES_N, false, 2>, 1);
-    else if (p.x3) err = norm ? launch(tapconv_kernel<BM, BN, WAVES_M, WAVES_N, true, 1>, 2)
-                              : launch(tapconv_kernel<BM, BN, WAVES_M, WAVES_N, false, 1>, 3);
+    const int loop = cfg_loop(p);
+    if (loop == BCOS_LOOP_BF16X3_PRESPLIT) err = norm ? launch(tapconv_kernel<BM, BN, WAVES_M, WAVES_N, true, 2>, 0)
+                                                      : launch(tapconv_kernel<BM, BN, WAVES_M, WAVES_N, false, 2>, 1);
+    else if (loop == BCOS_LOOP_BF16X3) err = norm ? launch(tapconv_kernel<BM, BN, WAVES_M, WAVES_N, true, 1>, 2)
+                                                  : launch(tapconv_kernel<BM, BN, WAVES_M, WAVES_N, false, 1>, 3);
     else err = norm ? launch(tapconv_kernel<BM, BN, WAVES_M, WAVES_N, true, 0>, 4)
                     : launch(tapconv_kernel<BM, BN, WAVES_M, WAVES_N, false, 0>, 5);
     if (err != hipSuccess) return bcos_set_hip_error("hipFuncSetAttribute", err);
@@ -3359,81 +3365,90 @@ extern "C" int BCOS_PH_NAME(BCOS_TAPCONV_PART)(unsigned long long* out) {
 #endif
 #define BCOS_TC_IN(k) (BCOS_TAPCONV_PART == -1 || BCOS_TAPCONV_PART == (k))
 #define BCOS_TC_LAUNCHER(name) __attribute__((visibility("hidden"))) int name(const void* kargs, int norm, hipStream_t s)
-BCOS_TC_LAUNCHER(bcos_tc_cfg_128x128);
-BCOS_TC_LAUNCHER(bcos_tc_cfg_128x64);
-BCOS_TC_LAUNCHER(bcos_tc_cfg_128x32);
-BCOS_TC_LAUNCHER(bcos_tc_h2_128x256);
-BCOS_TC_LAUNCHER(bcos_tc_h2_128x128);
-BCOS_TC_LAUNCHER(bcos_tc_h2_128x64);
-BCOS_TC_LAUNCHER(bcos_tc_h2_128x32);
-BCOS_TC_LAUNCHER(bcos_tc_h2_256x64);
-BCOS_TC_LAUNCHER(bcos_tc_h2_256x32);
-BCOS_TC_LAUNCHER(bcos_tc_d_128x256);
-BCOS_TC_LAUNCHER(bcos_tc_d_128x128);
-BCOS_TC_LAUNCHER(bcos_tc_d_128x192);
-BCOS_TC_LAUNCHER(bcos_tc_d_128x64);
-BCOS_TC_LAUNCHER(bcos_tc_d_128x32);
-BCOS_TC_LAUNCHER(bcos_tc_d_256x64);
-BCOS_TC_LAUNCHER(bcos_tc_d_256x32);
-BCOS_TC_LAUNCHER(bcos_tc_p_128x256_a);
-BCOS_TC_LAUNCHER(bcos_tc_p_128x128_a);
-BCOS_TC_LAUNCHER(bcos_tc_p_128x128_b);
-BCOS_TC_LAUNCHER(bcos_tc_p_128x128_c);
-BCOS_TC_LAUNCHER(bcos_tc_p_256x64_a);
-BCOS_TC_LAUNCHER(bcos_tc_p2_256x32_t16);
-BCOS_TC_LAUNCHER(bcos_tc_p2_256x32_t9);
-BCOS_TC_LAUNCHER(bcos_tc_p2_256x64_b32);
-#define BCOS_TC_DEFINE(name, call) BCOS_TC_LAUNCHER(name) { return call(*static_cast<const KArgs*>(kargs), norm != 0, s); }
+// every tile launcher, once: X(name, launcher family = which loop it instantiates, tile rows, tile columns).  The list declares the launchers, numbers them (the route ids of
+// bcos_tapconv_route_query, the narrow-output kernel of bcos_skinny.hip last) and fills the table the dispatcher launches through;
+// BCOS_TC_DEFINE refuses a launcher that is not in it, and one that is listed without a definition does not link
+enum : int { BCOS_FAM_CFG, BCOS_FAM_H2, BCOS_FAM_D, BCOS_FAM_P };      // launch_cfg / launch_h2 / launch_d / launch_p
+#define BCOS_TC_ROUTES(X) \
+    X(cfg_128x128, BCOS_FAM_CFG, 128, 128) \
+    X(cfg_128x64, BCOS_FAM_CFG, 128, 64) \
+    X(cfg_128x32, BCOS_FAM_CFG, 128, 32) \
+    X(h2_128x256, BCOS_FAM_H2, 128, 256) \
+    X(h2_128x128, BCOS_FAM_H2, 128, 128) \
+    X(h2_128x64, BCOS_FAM_H2, 128, 64) \
+    X(h2_128x32, BCOS_FAM_H2, 128, 32) \
+    X(h2_256x64, BCOS_FAM_H2, 256, 64) \
+    X(h2_256x32, BCOS_FAM_H2, 256, 32) \
+    X(d_128x256, BCOS_FAM_D, 128, 256) \
+    X(d_128x128, BCOS_FAM_D, 128, 128) \
+    X(d_128x192, BCOS_FAM_D, 128, 192) \
+    X(d_128x64, BCOS_FAM_D, 128, 64) \
+    X(d_128x32, BCOS_FAM_D, 128, 32) \
+    X(d_256x64, BCOS_FAM_D, 256, 64) \
+    X(d_256x32, BCOS_FAM_D, 256, 32) \
+    X(p_128x256_a, BCOS_FAM_P, 128, 256) \
+    X(p_128x128_a, BCOS_FAM_P, 128, 128) \
+    X(p_128x128_b, BCOS_FAM_P, 128, 128) \
+    X(p_128x128_c, BCOS_FAM_P, 128, 128) \
+    X(p_256x64_a, BCOS_FAM_P, 256, 64) \
+    X(p2_256x32_t16, BCOS_FAM_P, 256, 32) \
+    X(p2_256x32_t9, BCOS_FAM_P, 256, 32) \
+    X(p2_256x64_b32, BCOS_FAM_P, 256, 64)
+#define BCOS_TC_X_DECL(name, fam, bm, bn) BCOS_TC_LAUNCHER(bcos_tc_##name);
+BCOS_TC_ROUTES(BCOS_TC_X_DECL)
+#define BCOS_TC_X_ID(name, fam, bm, bn) ROUTE_##name,
+enum : int { BCOS_TC_ROUTES(BCOS_TC_X_ID) ROUTE_skinny, ROUTE_COUNT };
+#define BCOS_TC_DEFINE(name, call) static_assert(ROUTE_##name >= 0, "launcher missing from BCOS_TC_ROUTES"); BCOS_TC_LAUNCHER(bcos_tc_##name) { return call(*static_cast<const KArgs*>(kargs), norm != 0, s); }
 #if BCOS_TC_IN(1)
-BCOS_TC_DEFINE(bcos_tc_cfg_128x128, (launch_cfg<128, 128, 2, 2>))
+BCOS_TC_DEFINE(cfg_128x128, (launch_cfg<128, 128, 2, 2>))
 #endif
 #if BCOS_TC_IN(2)
-BCOS_TC_DEFINE(bcos_tc_cfg_128x64, (launch_cfg<128, 64, 2, 2>))
-BCOS_TC_DEFINE(bcos_tc_cfg_128x32, (launch_cfg<128, 32, 4, 1>))
+BCOS_TC_DEFINE(cfg_128x64, (launch_cfg<128, 64, 2, 2>))
+BCOS_TC_DEFINE(cfg_128x32, (launch_cfg<128, 32, 4, 1>))
 #endif
 #if BCOS_TC_IN(3)
-BCOS_TC_DEFINE(bcos_tc_h2_128x256, (launch_h2<128, 256, 2, 2>))
-BCOS_TC_DEFINE(bcos_tc_h2_128x128, (launch_h2<128, 128, 2, 2>))
+BCOS_TC_DEFINE(h2_128x256, (launch_h2<128, 256, 2, 2>))
+BCOS_TC_DEFINE(h2_128x128, (launch_h2<128, 128, 2, 2>))
 #endif
 #if BCOS_TC_IN(4)
-BCOS_TC_DEFINE(bcos_tc_h2_256x64, (launch_h2<256, 64, 4, 1>))
-BCOS_TC_DEFINE(bcos_tc_h2_256x32, (launch_h2<256, 32, 4, 1>))
+BCOS_TC_DEFINE(h2_256x64, (launch_h2<256, 64, 4, 1>))
+BCOS_TC_DEFINE(h2_256x32, (launch_h2<256, 32, 4, 1>))
 #endif
 #if BCOS_TC_IN(5)
 #ifndef D_WIDE_WM
 #define D_WIDE_WM 4                // development switch: wave layout of the 128 x 256 LDS-DMA configuration (4 x 1; 2 x 2 measured in round 4)
 #define D_WIDE_WN 1
 #endif
-BCOS_TC_DEFINE(bcos_tc_d_128x256, (launch_d<128, 256, D_WIDE_WM, D_WIDE_WN>))
+BCOS_TC_DEFINE(d_128x256, (launch_d<128, 256, D_WIDE_WM, D_WIDE_WN>))
 #endif
 #if BCOS_TC_IN(6)
-BCOS_TC_DEFINE(bcos_tc_d_128x128, (launch_d<128, 128, 4, 1>))
-BCOS_TC_DEFINE(bcos_tc_d_128x64, (launch_d<128, 64, 4, 1>))
+BCOS_TC_DEFINE(d_128x128, (launch_d<128, 128, 4, 1>))
+BCOS_TC_DEFINE(d_128x64, (launch_d<128, 64, 4, 1>))
 #endif
 #if BCOS_TC_IN(8)
-BCOS_TC_DEFINE(bcos_tc_d_128x192, (launch_d<128, 192, 4, 1>))
+BCOS_TC_DEFINE(d_128x192, (launch_d<128, 192, 4, 1>))
 #endif
 #if BCOS_TC_IN(7)
-BCOS_TC_DEFINE(bcos_tc_d_256x64, (launch_d<256, 64, 4, 1>))
-BCOS_TC_DEFINE(bcos_tc_d_256x32, (launch_d<256, 32, 4, 1>))
-BCOS_TC_DEFINE(bcos_tc_d_128x32, (launch_d<128, 32, 4, 1>))
+BCOS_TC_DEFINE(d_256x64, (launch_d<256, 64, 4, 1>))
+BCOS_TC_DEFINE(d_256x32, (launch_d<256, 32, 4, 1>))
+BCOS_TC_DEFINE(d_128x32, (launch_d<128, 32, 4, 1>))
 #endif
 // input-patch configurations: <BM, BN, waves M x N, items per thread (128 pixels each), LDS pixels, taps>
 #if BCOS_TC_IN(9)
-BCOS_TC_DEFINE(bcos_tc_p_128x256_a, (launch_p<128, 256, 2, 2, 2, 256, 9>))      // 14^2: 15 rows of 16
-BCOS_TC_DEFINE(bcos_tc_p_256x64_a, (launch_p<256, 64, 4, 1, 5, 640, 9>))        // 56^2: 10 rows of 58 (pitch 64)
-BCOS_TC_DEFINE(bcos_tc_p2_256x64_b32, (launch_p<256, 64, 4, 1, 3, 640, 9, 32>))      // 3 x 3 on wide images: 8 x 32 blocks, 10 rows of 34 (pitch 64)
-BCOS_TC_DEFINE(bcos_tc_p2_256x32_t9, (launch_p<256, 32, 4, 1, 3, 576, 9, 16>))     // 3 x 3 with <= 32 output channels on wide images (CLIP stem, 32 -> 32 @112^2): 16 x 16 blocks, 18 rows of 18
-BCOS_TC_DEFINE(bcos_tc_p2_256x32_t16, (launch_p<256, 32, 4, 1, 3, 608, 16, 16>))   // 4 x 4 taps (the depth-to-space stem gradient): 16 x 16 blocks, 19 rows of 19 (pitch 32)
+BCOS_TC_DEFINE(p_128x256_a, (launch_p<128, 256, 2, 2, 2, 256, 9>))      // 14^2: 15 rows of 16
+BCOS_TC_DEFINE(p_256x64_a, (launch_p<256, 64, 4, 1, 5, 640, 9>))        // 56^2: 10 rows of 58 (pitch 64)
+BCOS_TC_DEFINE(p2_256x64_b32, (launch_p<256, 64, 4, 1, 3, 640, 9, 32>))      // 3 x 3 on wide images: 8 x 32 blocks, 10 rows of 34 (pitch 64)
+BCOS_TC_DEFINE(p2_256x32_t9, (launch_p<256, 32, 4, 1, 3, 576, 9, 16>))     // 3 x 3 with <= 32 output channels on wide images (CLIP stem, 32 -> 32 @112^2): 16 x 16 blocks, 18 rows of 18
+BCOS_TC_DEFINE(p2_256x32_t16, (launch_p<256, 32, 4, 1, 3, 608, 16, 16>))   // 4 x 4 taps (the depth-to-space stem gradient): 16 x 16 blocks, 19 rows of 19 (pitch 32)
 #endif
 #if BCOS_TC_IN(10)
-BCOS_TC_DEFINE(bcos_tc_p_128x128_a, (launch_p<128, 128, 2, 2, 2, 256, 9>))      // 14^2
-BCOS_TC_DEFINE(bcos_tc_p_128x128_b, (launch_p<128, 128, 2, 2, 2, 448, 9>))      // 7^2: 28 rows of 9 (pitch 16)
-BCOS_TC_DEFINE(bcos_tc_p_128x128_c, (launch_p<128, 128, 2, 2, 3, 320, 9>))      // 28^2: 10 rows of 30 (pitch 32)
+BCOS_TC_DEFINE(p_128x128_a, (launch_p<128, 128, 2, 2, 2, 256, 9>))      // 14^2
+BCOS_TC_DEFINE(p_128x128_b, (launch_p<128, 128, 2, 2, 2, 448, 9>))      // 7^2: 28 rows of 9 (pitch 16)
+BCOS_TC_DEFINE(p_128x128_c, (launch_p<128, 128, 2, 2, 3, 320, 9>))      // 28^2: 10 rows of 30 (pitch 32)
 #endif
 #if BCOS_TC_IN(0)
-BCOS_TC_DEFINE(bcos_tc_h2_128x64, (launch_h2<128, 64, 2, 2>))
-BCOS_TC_DEFINE(bcos_tc_h2_128x32, (launch_h2<128, 32, 4, 1>))
+BCOS_TC_DEFINE(h2_128x64, (launch_h2<128, 64, 2, 2>))
+BCOS_TC_DEFINE(h2_128x32, (launch_h2<128, 32, 4, 1>))
 
 extern "C" int bcos_set_contraction_mode(int mode) {
     if (mode < 0 || mode > 2)
@@ -3922,7 +3937,33 @@ extern "C" int bcos_tapconv_presplit(const float* a, const float* wt, const void
     return bcos_tapconv_ops(&o, geom, epi, stream);
 }
 
-namespace { thread_local bool t_query_image_range = false; }
+namespace {
+thread_local bool t_query_image_range = false;
+thread_local bcos_tapconv_route* t_query_route = nullptr;       // bcos_tapconv_route_query: where the dispatch reports instead of launching
+
+struct RouteEntry { const char* name; int fam, bm, bn; int (*launch)(const void*, int, hipStream_t); };
+#define BCOS_TC_X_ROW(name, fam, bm, bn) {#name, fam, bm, bn, bcos_tc_##name},
+const RouteEntry ROUTES[ROUTE_COUNT] = {BCOS_TC_ROUTES(BCOS_TC_X_ROW) {"skinny", -1, 0, 0, nullptr}};
+
+// the ONE place a tile launcher is entered from: a query records the route and stops here
+inline int route_go(int id, const KArgs& p, bool norm, hipStream_t s) {
+    if (bcos_tapconv_route* r = t_query_route) {
+        const int fam = ROUTES[id].fam;
+        r->route = id;
+        r->epi_kind = p.epi_kind;
+        r->norm = norm ? 1 : 0;
+        r->loop = fam == BCOS_FAM_CFG ? cfg_loop(p)      // (what launch_cfg asks itself)
+                  : fam == BCOS_FAM_H2 ? BCOS_LOOP_F16X2_REGS : fam == BCOS_FAM_D ? BCOS_LOOP_F16X2_DMA : BCOS_LOOP_F16X2_PATCH;
+        r->bm = ROUTES[id].bm;
+        r->bn = ROUTES[id].bn;
+        r->chunks = 1;
+        r->ch_pass = 0;
+        return BCOS_OK;
+    }
+    return ROUTES[id].launch(&p, norm ? 1 : 0, s);
+}
+#define BCOS_TC_GO(name) route_go(ROUTE_##name, p, norm, s)
+}  // namespace
 
 extern "C" int bcos_tapconv_ops(const bcos_operands* ops, const bcos_tapconv_geom* geom, const bcos_epilogue* epi, void* stream);
 
@@ -3936,6 +3977,19 @@ extern "C" int bcos_tapconv_fuses_image_range(const bcos_operands* ops, const bc
     t_query_image_range = false;
     return rc;
 }
+
+extern "C" int bcos_tapconv_route_query(const bcos_operands* ops, const bcos_tapconv_geom* geom, const bcos_epilogue* epi, bcos_tapconv_route* out) {
+    if (!out) return bcos_set_error(BCOS_E_INVAL, "bcos_tapconv_route_query: NULL result");
+    *out = bcos_tapconv_route{-1, 0, 0, 0, 0, 0, 0, 0};
+    t_query_route = out;
+    const int rc = bcos_tapconv_ops(ops, geom, epi, nullptr);
+    t_query_route = nullptr;
+    return rc;
+}
+
+extern "C" const char* bcos_tapconv_route_name(int route) { return route >= 0 && route < ROUTE_COUNT ? ROUTES[route].name : nullptr; }
+extern "C" int bcos_tapconv_route_count(void) { return ROUTE_COUNT; }
+extern "C" int bcos_tapconv_epilogue_kinds(void) { return N_EPI_KINDS; }
 
 extern "C" int bcos_tapconv_ops(const bcos_operands* ops, const bcos_tapconv_geom* geom, const bcos_epilogue* epi, void* stream) {
     if (!ops || !geom || !epi) return bcos_set_error(BCOS_E_INVAL, "bcos_tapconv: NULL argument");
@@ -4071,6 +4125,7 @@ extern "C" int bcos_tapconv_ops(const bcos_operands* ops, const bcos_tapconv_geo
                 if (o2.a_imgmin_c) o2.a_imgmin_c += n0;
                 const int rc = bcos_tapconv_ops(&o2, &g2, &e2, stream);
                 if (rc != BCOS_OK) return rc;
+                if (t_query_route) { t_query_route->chunks = (g.N + per - 1) / per; return BCOS_OK; }      // (the first chunk's route)
             }
             return BCOS_OK;
         }
@@ -4157,7 +4212,9 @@ extern "C" int bcos_tapconv_ops(const bcos_operands* ops, const bcos_tapconv_geo
     const bool norm = epi->bcos_mode != BCOS_NONE;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (g.Cout <= 8 && G == 1 && !epi->out_absmax && !epi->out2_absmax && epi->max_out <= 1 && epi->addend_sub <= 1 && !epi->row_scale && !epi->a_sumsq && !epi->rowadd) {
-        const int handled = bcos_try_skinny(a, wt, p.g, p.e, p.M, s);
+        int ch_pass = 0;
+        const int handled = bcos_try_skinny(a, wt, p.g, p.e, p.M, s, t_query_route ? &ch_pass : nullptr);
+        if (handled > 0 && t_query_route) *t_query_route = bcos_tapconv_route{ROUTE_skinny, 0, 0, BCOS_LOOP_F32, 0, 0, 1, ch_pass};
         if (handled != 0) return handled < 0 ? handled : BCOS_OK;
     }
     if (p.h2) {
@@ -4174,17 +4231,17 @@ extern "C" int bcos_tapconv_ops(const bcos_operands* ops, const bcos_tapconv_geo
                                  g.dstep_h == 1 && g.dstep_w == 1 && p.g.a_pitch >= g.C;
             if (dma && geom_ok && p.a_imgmax && patch_on && !epi->row_scale && !epi->a_sumsq) {      // (the patch kernels compile those two out)
                 if (ntaps == 16) {
-                    if (g.Cout <= 32 && g.in_sh == 1) return bcos_tc_p2_256x32_t16(&p, norm, s);
+                    if (g.Cout <= 32 && g.in_sh == 1) return BCOS_TC_GO(p2_256x32_t16);
                 } else {
-                if (g.Cout > 128 && g.Cout <= 256 && patch_fits(g, 128, 256, 256) && bcos_option(BCOS_OPT_PATCH_WIDE)) return bcos_tc_p_128x256_a(&p, norm, s);
-                if (g.Cout > 64 && patch_fits(g, 128, 256, 256)) return bcos_tc_p_128x128_a(&p, norm, s);
-                if (g.Cout > 64 && patch_fits(g, 128, 256, 448)) return bcos_tc_p_128x128_b(&p, norm, s);
-                if (g.Cout > 64 && patch_fits(g, 128, 384, 320)) return bcos_tc_p_128x128_c(&p, norm, s);
-                if (g.Cout > 32 && g.Cout <= 64 && patch_fits(g, 256, 640, 640)) return bcos_tc_p_256x64_a(&p, norm, s);
+                if (g.Cout > 128 && g.Cout <= 256 && patch_fits(g, 128, 256, 256) && bcos_option(BCOS_OPT_PATCH_WIDE)) return BCOS_TC_GO(p_128x256_a);
+                if (g.Cout > 64 && patch_fits(g, 128, 256, 256)) return BCOS_TC_GO(p_128x128_a);
+                if (g.Cout > 64 && patch_fits(g, 128, 256, 448)) return BCOS_TC_GO(p_128x128_b);
+                if (g.Cout > 64 && patch_fits(g, 128, 384, 320)) return BCOS_TC_GO(p_128x128_c);
+                if (g.Cout > 32 && g.Cout <= 64 && patch_fits(g, 256, 640, 640)) return BCOS_TC_GO(p_256x64_a);
                 // wider images (112^2: the 3 x 3 stem convolutions of the CLIP ResNets): 8 x 32 blocks.  (At 56^2 the linear tiles win,
                 // 224 against 253 us: the blocks leave an eighth of the rows empty there.)
-                if (g.Cout > 32 && g.Cout <= 64 && g.in_sh == 1 && g.Q > 64) return bcos_tc_p2_256x64_b32(&p, norm, s);
-                if (g.Cout > 8 && g.Cout <= 32 && g.in_sh == 1 && g.Q > 64) return bcos_tc_p2_256x32_t9(&p, norm, s);
+                if (g.Cout > 32 && g.Cout <= 64 && g.in_sh == 1 && g.Q > 64) return BCOS_TC_GO(p2_256x64_b32);
+                if (g.Cout > 8 && g.Cout <= 32 && g.in_sh == 1 && g.Q > 64) return BCOS_TC_GO(p2_256x32_t9);
                 }
             }
         }
@@ -4197,8 +4254,8 @@ extern "C" int bcos_tapconv_ops(const bcos_operands* ops, const bcos_tapconv_geo
             const int64_t tm = (M64 + 127) / 128;
             const int64_t t128 = tm * ((g.Cout + 127) / 128);
             if (t128 < 64) {
-                if (tm * ((g.Cout + 63) / 64) >= 96 || g.Cout <= 128) return bcos_tc_d_128x64(&p, norm, s);
-                return bcos_tc_d_128x32(&p, norm, s);
+                if (tm * ((g.Cout + 63) / 64) >= 96 || g.Cout <= 128) return BCOS_TC_GO(d_128x64);
+                return BCOS_TC_GO(d_128x32);
             }
         }
         if (g.Cout > 64) {
@@ -4218,13 +4275,13 @@ extern "C" int bcos_tapconv_ops(const bcos_operands* ops, const bcos_tapconv_geo
             if (force) wide = g.Cout > 128 && force == 2;
             // 129 ... 192 columns (the 192-wide linears of the SimpleViTs: to_out, linear2, their gradients): ONE tile of 192 columns
             // (six accumulator tiles per wave) instead of 128 + a half-empty second 128
-            if (dma && g.Cout > 128 && g.Cout <= 192 && !force) return bcos_tc_d_128x192(&p, norm, s);
+            if (dma && g.Cout > 128 && g.Cout <= 192 && !force) return BCOS_TC_GO(d_128x192);
             // multiples of 192 that are not multiples of 256 (the 576-wide to_qkv of the SimpleViTs: 3 x 192 exactly, against 5 x 128 with
             // 64 empty columns or 3 x 256 with 192): whole 192-column tiles -- ViT-Ti batch 512 forward+explanation 18.26 -> 17.97 ms per step
             // in three same-node pairs (round 5); 768 = 4 x 192 against 3 x 256: no gain, stays on the 256-column tiles.  Bits unchanged.
-            if (dma && g.Cout % 192 == 0 && g.Cout % 256 != 0 && g.Cout <= 1152 && !force) return bcos_tc_d_128x192(&p, norm, s);
-            if (wide) return dma ? bcos_tc_d_128x256(&p, norm, s) : bcos_tc_h2_128x256(&p, norm, s);
-            return dma ? bcos_tc_d_128x128(&p, norm, s) : bcos_tc_h2_128x128(&p, norm, s);
+            if (dma && g.Cout % 192 == 0 && g.Cout % 256 != 0 && g.Cout <= 1152 && !force) return BCOS_TC_GO(d_128x192);
+            if (wide) return dma ? BCOS_TC_GO(d_128x256) : BCOS_TC_GO(h2_128x256);
+            return dma ? BCOS_TC_GO(d_128x128) : BCOS_TC_GO(h2_128x128);
         }
         if (g.Cout > 32) {
             // 256 x 64 tiles (four waves of 64 x 64: the A operand's split, its LDS image and the per-tile prologue / epilogue
@@ -4234,23 +4291,23 @@ extern "C" int bcos_tapconv_ops(const bcos_operands* ops, const bcos_tapconv_geo
             // K walk, same product order per accumulator).
             const bool tall = bcos_option(BCOS_OPT_H2_TALL) != 0;       // development switch: 0 keeps the 128-row tiles
             const int64_t tall_min = bcos_option(BCOS_OPT_H2_TALL_MIN);     // default 2 * 256 * SLOTS (batch 128, M = 401 408: +0.4 % per step; M = 200 704: neutral)
-            if (M64 >= tall_min && tall) return dma ? bcos_tc_d_256x64(&p, norm, s) : bcos_tc_h2_256x64(&p, norm, s);
-            return dma ? bcos_tc_d_128x64(&p, norm, s) : bcos_tc_h2_128x64(&p, norm, s);
+            if (M64 >= tall_min && tall) return dma ? BCOS_TC_GO(d_256x64) : BCOS_TC_GO(h2_256x64);
+            return dma ? BCOS_TC_GO(d_128x64) : BCOS_TC_GO(h2_128x64);
         }
         {   // 256 x 32 tiles likewise (the depth-to-space stem gradient, M = 3.2 M: 1.29-1.38 -> 1.17-1.20 ms in a same-node A/B)
-            if (M64 >= 2 * 256 * SLOTS && bcos_option(BCOS_OPT_H2_TALL)) return dma ? bcos_tc_d_256x32(&p, norm, s) : bcos_tc_h2_256x32(&p, norm, s);
+            if (M64 >= 2 * 256 * SLOTS && bcos_option(BCOS_OPT_H2_TALL)) return dma ? BCOS_TC_GO(d_256x32) : BCOS_TC_GO(h2_256x32);
         }
-        return dma ? bcos_tc_d_128x32(&p, norm, s) : bcos_tc_h2_128x32(&p, norm, s);
+        return dma ? BCOS_TC_GO(d_128x32) : BCOS_TC_GO(h2_128x32);
     }
     if (g.Cout > 64) {
         // few-row launches (see the split-f16 branch above): narrower column tiles put a workgroup on more CUs; same bits
         const int64_t tm = (M64 + 127) / 128;
         if (G == 1 && tm * ((g.Cout + 127) / 128) < 64 && bcos_option(BCOS_OPT_H2_TILE) == 0)
-            return (tm * ((g.Cout + 63) / 64) >= 96 || g.Cout <= 128) ? bcos_tc_cfg_128x64(&p, norm, s) : bcos_tc_cfg_128x32(&p, norm, s);
-        return bcos_tc_cfg_128x128(&p, norm, s);
+            return (tm * ((g.Cout + 63) / 64) >= 96 || g.Cout <= 128) ? BCOS_TC_GO(cfg_128x64) : BCOS_TC_GO(cfg_128x32);
+        return BCOS_TC_GO(cfg_128x128);
     }
-    if (g.Cout > 32) return bcos_tc_cfg_128x64(&p, norm, s);
-    return bcos_tc_cfg_128x32(&p, norm, s);
+    if (g.Cout > 32) return BCOS_TC_GO(cfg_128x64);
+    return BCOS_TC_GO(cfg_128x32);
 }
 
 

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define BCOS_ABI_VERSION 10
+#define BCOS_ABI_VERSION 11
 
 enum {
     BCOS_OK = 0,
@@ -326,6 +326,33 @@ int bcos_tapconv_ops(const bcos_operands* ops, const bcos_tapconv_geom* geom, co
 int bcos_tapconv_fuses_image_range(const bcos_operands* ops, const bcos_tapconv_geom* geom, const bcos_epilogue* epi);
 int bcos_tapconv(const float* a, const float* wt, const bcos_tapconv_geom* geom,
                  const bcos_epilogue* epi, void* stream);
+
+/* Which tile launcher, contraction loop and epilogue would bcos_tapconv_ops(ops, geom, epi, ...) run?  (ABI v11)  Launches nothing and needs no
+ * device: the call walks bcos_tapconv_ops' own validation, operand and epilogue selection and its dispatch, and stops where the launch would
+ * be issued -- the answer comes from the code that launches, under the option table and default contraction mode of the moment.  Returns 0 and
+ * fills *out, or the error code bcos_tapconv_ops returns for the same arguments (out == NULL: BCOS_E_INVAL).  Every compiled launcher has an
+ * id in [0, bcos_tapconv_route_count()); the ids are not stable across versions, the names are.  bcos_tapconv_group's fused narrow-output
+ * form (several tap sets in one launch) is outside the query: it reports what each entry would take on its own. */
+enum { BCOS_LOOP_F32 = 0,             /* v_mfma_f32_32x32x2_f32 (also the narrow-output kernel)    */
+       BCOS_LOOP_BF16X3 = 1,          /* 3-way bf16 split of both operands on the fly              */
+       BCOS_LOOP_BF16X3_PRESPLIT = 2, /* ... weights from the bcos_split_weights image             */
+       BCOS_LOOP_F16X2_REGS = 3,      /* split-f16, register-staged (BCOS_OPT_H2_LOOP = 1)         */
+       BCOS_LOOP_F16X2_DMA = 4,       /* split-f16, LDS-DMA staged                                 */
+       BCOS_LOOP_F16X2_PATCH = 5 };   /* split-f16 over an LDS-resident input patch (a_imgmax)     */
+typedef struct bcos_tapconv_route {
+    int32_t route;        /* id; bcos_tapconv_route_name(route) names it, e.g. "d_128x192", "p_128x128_b", "skinny"                   */
+    int32_t epi_kind;     /* 0 = general epilogue (always for "skinny": its own plain epilogue), k + 1 = specialised kind k of its direction */
+    int32_t norm;         /* 1 = B-cos launch (forward kinds), 0 = plain / gradient launch (backward kinds)                           */
+    int32_t loop;         /* BCOS_LOOP_*                                                                                               */
+    int32_t bm, bn;       /* tile rows / columns (0 for the narrow-output kernel)                                                      */
+    int32_t chunks;       /* 1, or the number of batch chunks of the BCOS_OPT_SPLIT_LIMIT path (the route is the first chunk's)        */
+    int32_t ch_pass;      /* narrow-output kernel: input channels staged per pass (< C: the channels are walked in slices); 0 otherwise */
+} bcos_tapconv_route;
+int bcos_tapconv_route_query(const bcos_operands* ops, const bcos_tapconv_geom* geom, const bcos_epilogue* epi, bcos_tapconv_route* out);
+const char* bcos_tapconv_route_name(int route);   /* NULL outside [0, bcos_tapconv_route_count()) */
+int bcos_tapconv_route_count(void);
+/* Number of specialised epilogue kinds per direction (epi_kind runs over 0 .. this). */
+int bcos_tapconv_epilogue_kinds(void);
 
 /* Pre-split, pre-scaled weights for the f16x2 contraction: wt [rows][Ktot] fp32 -> image
  * [32-row tile][16-k step][plane h|l][lane][8 f16] (B fragments of v_mfma_f32_32x32x16_f16; rows padded to a multiple of

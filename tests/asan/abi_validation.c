@@ -166,6 +166,27 @@ int main(void) {
       EXPECT(bcos_tapconv_ops(&o, &g, &e, NULL), BCOS_E_NOSUP); e.out_imgmax = NULL; }
     { e.rowadd = buf;                                                               /* a row-scaled addend without its scales */
       EXPECT(bcos_tapconv_ops(&o, &g, &e, NULL), BCOS_E_NOSUP); e.rowadd = NULL; }
+    /* ABI v11: the route query walks the same validation and launches nothing */
+    { bcos_tapconv_route r; int i, n = bcos_tapconv_route_count();
+      EXPECT(bcos_tapconv_route_query(NULL, &g, &e, &r), BCOS_E_INVAL);
+      EXPECT(bcos_tapconv_route_query(&o, NULL, &e, &r), BCOS_E_INVAL);
+      EXPECT(bcos_tapconv_route_query(&o, &g, NULL, &r), BCOS_E_INVAL);
+      EXPECT(bcos_tapconv_route_query(&o, &g, &e, NULL), BCOS_E_INVAL);
+      g.C = 6;          EXPECT(bcos_tapconv_route_query(&o, &g, &e, &r), BCOS_E_INVAL); g.C = 8;
+      o.a = buf + 1;    EXPECT(bcos_tapconv_route_query(&o, &g, &e, &r), BCOS_E_INVAL); o.a = buf;
+      e.addend_sub = 2; EXPECT(bcos_tapconv_route_query(&o, &g, &e, &r), BCOS_E_INVAL); e.addend_sub = 0;
+      e.rowadd = buf;   EXPECT(bcos_tapconv_route_query(&o, &g, &e, &r), BCOS_E_NOSUP); e.rowadd = NULL;
+      EXPECT(bcos_tapconv_route_query(&o, &g, &e, &r), BCOS_OK);                     /* 16 rows x 8 columns, plain: the narrow-output kernel */
+      if (r.route != n - 1 || strcmp(bcos_tapconv_route_name(r.route), "skinny") != 0 || r.ch_pass != 8 || r.chunks != 1) {
+          printf("FAIL route of the narrow launch: %d\n", r.route); ++failures; }
+      e.bcos_mode = BCOS_CONV_EPS; o.contraction = BCOS_CONTRACT_F32;
+      EXPECT(bcos_tapconv_route_query(&o, &g, &e, &r), BCOS_OK);                     /* B-cos launch: a tile launcher, fp32 loop, kind of the bare form */
+      if (strcmp(bcos_tapconv_route_name(r.route), "cfg_128x32") != 0 || r.loop != BCOS_LOOP_F32 || r.norm != 1 || r.epi_kind == 0 || r.bm != 128 || r.bn != 32) {
+          printf("FAIL route of the small B-cos launch: %d\n", r.route); ++failures; }
+      e.bcos_mode = BCOS_NONE; o.contraction = 0;
+      if (n < 2 || bcos_tapconv_route_name(-1) || bcos_tapconv_route_name(n)) { printf("FAIL route names outside the table\n"); ++failures; }
+      for (i = 0; i < n; ++i) if (!bcos_tapconv_route_name(i) || !*bcos_tapconv_route_name(i)) { printf("FAIL route %d has no name\n", i); ++failures; }
+      if (bcos_tapconv_epilogue_kinds() != 8) { printf("FAIL epilogue kinds\n"); ++failures; } }
     EXPECT(bcos_weight_prep_batch(NULL, 1, 64, 64, am, NULL), BCOS_E_INVAL);
     EXPECT(bcos_weight_prep_batch((const bcos_weight_prep_job*)buf, 1, 64, 64, NULL, NULL), BCOS_E_INVAL);     /* no scratch for the rows' maxima */
     EXPECT(bcos_weight_prep_batch((const bcos_weight_prep_job*)buf, 0, 64, 64, am, NULL), BCOS_E_INVAL);
