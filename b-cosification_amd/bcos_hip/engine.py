@@ -106,6 +106,19 @@ def _interleave(gens, streams, arenas, device):
     return results
 
 
+def check_occluded_input(x, rects):
+    """forward(x, occlude=rects) of both engines: one contiguous 6-channel device image and a device bank [n, 4]; -> (x, n)"""
+    if x.dim() != 4 or x.shape[0] != 1 or x.shape[1] != 6:
+        raise ValueError(f"forward(x, occlude=...): expected ONE 6-channel image [1,6,H,W] (the masks multiply the network input; "
+                         f"masking before AddInverse is a different operator), got {tuple(x.shape)}")
+    ops.require_device(x, "bcos_hip.engine")
+    if not (torch.is_tensor(rects) and rects.is_cuda and rects.device == x.device and rects.dtype == torch.int32 and rects.dim() == 2
+            and rects.shape[1] == 4 and rects.is_contiguous() and rects.shape[0] > 0):
+        raise ValueError("forward(x, occlude=...): the mask bank is a contiguous int32 tensor [n, 4] of rectangles on the image's device")
+    x = x.detach()
+    return (x if x.is_contiguous() else x.contiguous()), rects.shape[0]
+
+
 def _pair(v):
     return (v, v) if isinstance(v, int) else (int(v[0]), int(v[1]))
 
@@ -500,9 +513,10 @@ class ResNetEngine:
     def _run_forward(self, x: torch.Tensor, keep: bool, gates=None):
         return _drive(self._run_forward_gen(x, keep, gates))
 
-    def _run_forward_gen(self, x: torch.Tensor, keep: bool, gates=None):
+    def _run_forward_gen(self, x: torch.Tensor, keep: bool, gates=None, occlude=None):
         """The forward pass as a generator: it yields (nothing) behind the stem and behind every block, so that the passes of several
-        sub-batches can be ISSUED interleaved (see _interleave); its return value is (head output, kept state)."""
+        sub-batches can be ISSUED interleaved (see _interleave); its return value is (head output, kept state).
+        `occlude` = (bank, first, n): the batch is the n copies of the ONE image x occluded by bank[first:first + n] (forward only)."""
         if x.dim() != 4 or x.shape[1] not in (3, 6):
             raise ValueError(f"expected [N,6,H,W] (or [N,3,H,W] to be AddInverse-encoded), got {tuple(x.shape)}")
         ops.require_device(x, "bcos_hip.engine")
@@ -511,7 +525,10 @@ class ResNetEngine:
         x = x if x.is_contiguous() else x.contiguous()
         mean, std = self._consts(x.device)
         add_inverse = x.shape[1] == 3
-        xn = ops.prep_input(x, mean, std, cpad=8, add_inverse=add_inverse, want_absmax=True)
+        if occlude is None:
+            xn = ops.prep_input(x, mean, std, cpad=8, add_inverse=add_inverse, want_absmax=True)
+        else:
+            xn = ops.prep_input_occluded(x, occlude[0], mean, std, first=occlude[1], n=occlude[2], cpad=8, want_absmax=True)
         gates = list(gates) if gates is not None else None
         if gates is not None and any(b.hybrid for b in self.blocks):
             raise BcosHipError("engine: replayed ReLU gates are not available for networks with a block on the nn.Module path (hybrid node)")
@@ -701,7 +718,12 @@ class ResNetEngine:
         return ops.ensure_absmax(g_lin.reshape(N, H, W, C).contiguous())
 
     @torch.no_grad()
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, occlude: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """`occlude` (a device bank [n, 4] of int32 rectangles, include/bcos_hip.h): x is ONE 6-channel image [1, 6, H, W] and the result
+        the head output [n, ...] of its n occluded copies `x * mask_i` (occlusion.py:80-90) -- the copies are never built: the prepared
+        input comes from ops.prep_input_occluded, everything behind it is the plan of an n-image batch, sub-batch streams included."""
+        if occlude is not None:
+            return self._forward_occluded(x, occlude)
         S = self._n_subbatches(x) if self.head_kind != "attn_unpool" else 1
         if S > 1:                                  # sub-batches on side streams (see _SUBBATCH_STREAMS)
             streams, arenas = self._side_for(x, S)
@@ -720,6 +742,25 @@ class ResNetEngine:
             return torch.cat(parts)
         with ops.absmax_arena(self._absmax_arena, x.device):
             return self._run_forward(x, keep=False)[0]
+
+    def _forward_occluded(self, x, rects):
+        x, n = check_occluded_input(x, rects)
+        S = min(int(self.subbatch_streams), n // _SUBBATCH_MIN) if self.head_kind != "attn_unpool" else 1
+        if S <= 1 or torch.cuda.is_current_stream_capturing():
+            with ops.absmax_arena(self._absmax_arena, x.device):
+                return _drive(self._run_forward_gen(x, keep=False, occlude=(rects, 0, n)))[0]
+        streams, arenas = self._side_for(x, S)
+        cur = torch.cuda.current_stream()
+        for i in range(S):
+            streams[i].wait_stream(cur)
+        cuts = [(n * i) // S for i in range(S + 1)]              # (the cuts of forward() on an n-image batch)
+        parts = [r[0] for r in _interleave([self._run_forward_gen(x, keep=False, occlude=(rects, cuts[i], cuts[i + 1] - cuts[i]))
+                                            for i in range(S)], streams, arenas, x.device)]
+        for st in streams[:S]:
+            cur.wait_stream(st)
+        for t in parts:
+            t.record_stream(cur)
+        return torch.cat(parts)
 
     @torch.no_grad()
     def explain(self, x: torch.Tensor, targets: Optional[torch.Tensor] = None, want_weights: bool = True,

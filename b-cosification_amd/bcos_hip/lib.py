@@ -19,7 +19,7 @@ LIB_PATH = Path(os.environ["BCOS_HIP_LIB"]) if os.environ.get("BCOS_HIP_LIB") el
 CSRC = PKG_ROOT / "csrc"
 INCLUDE = REPO_ROOT / "include"
 SOURCES = ["bcos_tapconv.hip", "bcos_skinny.hip", "bcos_elementwise.hip", "bcos_vit.hip", "bcos_render.hip", "bcos_train.hip",
-           "bcos_agc.hip", "bcos_abi.hip"]
+           "bcos_agc.hip", "bcos_occlusion.hip", "bcos_abi.hip"]
 
 BCOS_NONE, BCOS_CONV_EPS, BCOS_LINEAR_EPS = 0, 1, 2
 BCOS_EPI_NORM_ONLY = 1
@@ -29,7 +29,7 @@ BCOS_EPI_GATE2_FROM_MUL = 8
 BCOS_EPI_MUL_FROM_ACT = 16
 BCOS_EPI_UNIT_NORM_W = 32
 BCOS_E_NOSUP = -95
-ABI_VERSION = 11
+ABI_VERSION = 12
 VERSION_DEV_FLAG = 0x40000000          # include/bcos_hip.h: BCOS_VERSION_DEV_FLAG
 TAPCONV_PARTS = 11
 
@@ -175,6 +175,8 @@ SIGNATURES = {
     "bcos_box_filter": (C.c_int, [_P, _P, _I, _I, _I, _I, _P]),
     "bcos_localisation_fractions": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "bcos_agc_clip": (C.c_int, [C.POINTER(AgcTensor), _I, _F, _F, _P]),
+    "bcos_prep_input_occluded": (C.c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "bcos_occlusion_accumulate": (C.c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
 }
 
 _lib = None

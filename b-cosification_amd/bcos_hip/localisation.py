@@ -37,16 +37,21 @@ def make_multi_images(imgs: torch.Tensor, g: int) -> torch.Tensor:
 
 @torch.no_grad()
 def grid_pointing_game(engine, multi_imgs: torch.Tensor, targets: torch.Tensor, single_shape: int, smooth: int = 0,
-                       neg: bool = False, attributions: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+                       neg: bool = False, attributions: Optional[torch.Tensor] = None, explainer=None) -> Dict[str, torch.Tensor]:
     """multi_imgs [B, C, g*s, g*s] (s = single_shape), targets [B, T] (the class of every grid cell, T = g*g, in the
     image order of make_multi_image) ->
         attributions [B, T, H, W]   contribution map of target t on multi-image b (= attribute_selection(...).sum(1)),
         fractions    [B, T, T]      share of the (smoothed, positive) attribution of target t inside cell c,
-        metric       [B, T]         fractions[b, t, t]: the localisation score of localisation.py:402."""
+        metric       [B, T]         fractions[b, t, t]: the localisation score of localisation.py:402.
+    `explainer` (an object with the reference's `attribute_selection(img, tgts)`, e.g. get_explainer(net, "Occlusion", "Occ9")): the
+    attributions are `explainer.attribute_selection(multi_img, tgts).sum(1)` per multi-image, as the reference's harness obtains them
+    for every explainer (localisation.py:417-466); `engine` is not used then."""
     B = multi_imgs.shape[0]
     tg = torch.as_tensor(targets, device=multi_imgs.device, dtype=torch.int64).view(B, -1)
     T = tg.shape[1]
-    if attributions is None:
+    if attributions is None and explainer is not None:
+        attributions = torch.stack([explainer.attribute_selection(multi_imgs[b:b + 1], tg[b].tolist()).sum(1) for b in range(B)])
+    elif attributions is None:
         attributions = engine.explain_targets(multi_imgs, tg)["contribution_maps"]
     H, W = attributions.shape[-2:]
     att = attributions.reshape(B * T, H, W).contiguous()

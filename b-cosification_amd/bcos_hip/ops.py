@@ -1017,6 +1017,66 @@ def prep_input(x_nchw, mean6, std6, cpad=8, add_inverse=False, want_absmax=False
     return out
 
 
+def _rect_bank(rects, what):
+    if not (torch.is_tensor(rects) and rects.dtype == torch.int32 and rects.dim() == 2 and rects.shape[1] == 4 and rects.is_contiguous()):
+        raise BcosHipError(f"{what}: a mask bank is a contiguous int32 tensor [n, 4] of rectangles (r0, r1, c0, c1)")
+    return rects
+
+
+def prep_input_occluded(x_nchw, rects, mean6, std6, first=0, n=None, cpad=8, want_absmax=False):
+    """The prepared input [n, H, W, cpad] of the copies of ONE image x_nchw [1, 6, H, W] occluded by rects[first:first + n] (a device
+    bank [*, 4] of int32 rectangles): what prep_input returns for `x_nchw * mask_i`, bit for bit, from one launch that never stores the
+    masked batch (include/bcos_hip.h: bcos_prep_input_occluded)."""
+    lib = _l.load()
+    _rect_bank(rects, "prep_input_occluded")
+    n = rects.shape[0] - first if n is None else int(n)
+    if x_nchw.dim() != 4 or x_nchw.shape[0] != 1:
+        raise BcosHipError(f"prep_input_occluded: one image [1, 6, H, W] at a time, got {tuple(x_nchw.shape)}")
+    if first < 0 or n <= 0 or first + n > rects.shape[0]:
+        raise BcosHipError(f"prep_input_occluded: masks [{first}, {first + n}) of a bank of {rects.shape[0]}")
+    if not rects.is_cuda or rects.device != x_nchw.device:
+        raise BcosHipError(f"prep_input_occluded: the mask bank is on {rects.device}, the image on {x_nchw.device}")
+    _, Cx, H, W = x_nchw.shape
+    out = torch.empty((n, H, W, cpad), device=x_nchw.device, dtype=torch.float32)
+    am = _fused_absmax(out, want_absmax)
+    _l.check(lib.bcos_prep_input_occluded(_dev(x_nchw, "x"), C.c_void_p(rects.data_ptr() + 16 * int(first)), _dev(out, "out"),
+                                          _dev(mean6, "mean"), _dev(std6, "std"), C.c_void_p(am.data_ptr()) if am is not None else None,
+                                          n, Cx, H, W, cpad, 0, _stream()), "bcos_prep_input_occluded")
+    return out
+
+
+def occlusion_accumulate(org, pert, rects, H, W, targets=None, only_positive=False, rects_host=None):
+    """org [CL], pert [n, CL] (logits of the image and of its n occluded copies, on the device), rects [n, 4] (device bank) ->
+    out [T, H, W]: per pixel and class the sum over the covering masks, in ascending order, of (org - pert[m]) / n_part[m]
+    (include/bcos_hip.h: bcos_occlusion_accumulate; occlusion.py:93-108).  `targets`: a sequence / tensor of class indices (validated
+    and wrapped on the host like every explained class), or None for all CL classes.  `rects_host`: the bank's host copy, which the
+    library validates (empty or unclipped rectangles); without it the bank is read back once here."""
+    lib = _l.load()
+    _rect_bank(rects, "occlusion_accumulate")
+    n, CL = pert.shape
+    if org.numel() != CL or rects.shape[0] != n:
+        raise BcosHipError(f"occlusion_accumulate: org {tuple(org.shape)}, pert {tuple(pert.shape)}, {rects.shape[0]} rectangles")
+    if rects_host is None:
+        rects_host = rects.cpu()
+    rects_host = _rect_bank(rects_host.contiguous(), "occlusion_accumulate (host copy)")
+    if rects_host.is_cuda or rects_host.shape[0] != n:
+        raise BcosHipError("occlusion_accumulate: rects_host must be the bank's copy in host memory")
+    tg = None
+    if targets is not None:
+        tg = check_targets(targets, CL, "occlusion_accumulate: targets").reshape(-1).to(device=pert.device, dtype=torch.int32).contiguous()
+        if tg.numel() == 0:
+            raise BcosHipError("occlusion_accumulate: no targets")
+    T = CL if tg is None else tg.numel()
+    out = torch.empty((T, H, W), device=pert.device, dtype=torch.float32)
+    if not rects.is_cuda:
+        raise BcosHipError(f"occlusion_accumulate: the mask bank is on {rects.device}")
+    _l.check(lib.bcos_occlusion_accumulate(_dev(org, "org"), _dev(pert, "pert"), C.c_void_p(rects.data_ptr()),
+                                           C.c_void_p(rects_host.data_ptr()), C.c_void_p(tg.data_ptr()) if tg is not None else None,
+                                           _dev(out, "out"), n, CL, T, int(H), int(W), 1 if only_positive else 0, _stream()),
+             "bcos_occlusion_accumulate")
+    return out
+
+
 def finalize_explanation(gxn, x_nchw, std6, add_inverse=False, want_weights=True, want_contrib=True, weights_out=None, contrib_out=None):
     """`weights_out` / `contrib_out`: write into these [N,6,H,W] / [N,H,W] tensors (slices of a larger batch) instead of new ones."""
     lib = _l.load()

@@ -286,8 +286,9 @@ class ViTEngine:
         from .engine import _drive
         return _drive(self._run_forward_gen(x, keep))
 
-    def _run_forward_gen(self, x, keep):
-        """the forward pass as a generator (yields behind the embedding and behind every encoder block: engine._interleave)"""
+    def _run_forward_gen(self, x, keep, occlude=None):
+        """the forward pass as a generator (yields behind the embedding and behind every encoder block: engine._interleave);
+        `occlude` = (bank, first, n): the batch is the n copies of the ONE image x occluded by bank[first:first + n] (forward only)"""
         if x.dim() != 4 or x.shape[1] not in (3, 6):
             raise ValueError(f"expected [N,6,H,W] (or [N,3,H,W] to be AddInverse-encoded), got {tuple(x.shape)}")
         ops.require_device(x, "bcos_hip.vit_engine")
@@ -298,7 +299,11 @@ class ViTEngine:
         p = self.patch
         mean, std = self._consts(x.device)
         add_inverse = x.shape[1] == 3
-        xn = ops.prep_input(x, mean, std, cpad=8, add_inverse=add_inverse, want_absmax=_F16X2)     # K = 2048 patch embedding
+        if occlude is None:
+            xn = ops.prep_input(x, mean, std, cpad=8, add_inverse=add_inverse, want_absmax=_F16X2)     # K = 2048 patch embedding
+        else:
+            N = occlude[2]
+            xn = ops.prep_input_occluded(x, occlude[0], mean, std, first=occlude[1], n=N, cpad=8, want_absmax=_F16X2)
         stem_st = []
         for layer in self.stem:          # conv stem: B-cos conv, GroupNorm (variance held constant in explanation mode), GELU gate
             hw_in = (xn.shape[1], xn.shape[2])
@@ -365,12 +370,12 @@ class ViTEngine:
             st.update(rstd_h=rstd_h, t_head=t_head)
         return logits, st
 
-    def _sub_batches(self, x, make_gen):
+    def _sub_batches(self, x, make_gen, n=None):
         """Run the pass generator make_gen(lo, hi) for contiguous sub-batches on side streams, their launches issued interleaved
         (bcos_hip/engine.py: _SUBBATCH_STREAMS, _interleave: images are independent, the sub-batches fill each other's launch tails)
         or once on the caller's stream."""
         from .engine import _SUBBATCH_MIN, _drive, _interleave
-        N = x.shape[0]
+        N = x.shape[0] if n is None else n          # (n: the batch is n occluded copies of the one image x)
         S = min(int(self.subbatch_streams), N // _SUBBATCH_MIN)
         if S <= 1 or not x.is_cuda or torch.cuda.is_current_stream_capturing():
             with _absmax_policy(), ops.absmax_arena(self._absmax_arena, x.device):
@@ -401,7 +406,18 @@ class ViTEngine:
         return outs
 
     @torch.no_grad()
-    def forward(self, x):
+    def forward(self, x, occlude: Optional[torch.Tensor] = None):
+        """`occlude` (a device bank [n, 4] of int32 rectangles): x is ONE image [1, 6, H, W] and the result the logits [n, classes] of
+        its n occluded copies (engine.ResNetEngine.forward): prepared by ops.prep_input_occluded, then the plan of an n-image batch."""
+        if occlude is not None:
+            from .engine import check_occluded_input
+            x, n = check_occluded_input(x, occlude)
+
+            def one_occluded(lo, hi):
+                logits, _ = yield from self._run_forward_gen(x, keep=False, occlude=(occlude, lo, hi - lo))
+                return logits
+            outs = self._sub_batches(x, one_occluded, n=n)
+            return outs[0] if len(outs) == 1 else torch.cat(outs)
         x = x.detach()
         x = x if x.is_contiguous() else x.contiguous()
 

@@ -2,13 +2,14 @@
 import warnings
 
 from interpretability.explanation_methods.explainers.captum import Grad, IxG
+from interpretability.explanation_methods.explainers.occlusion import Occlusion
 from interpretability.explanation_methods.explainers.ours import Ours, OursRelative
 from interpretability.explanation_methods.explanation_configs import explainer_configs
 
-explainer_map = {"IxG": IxG, "Grad": Grad, "Ours": Ours, "OursRelative": OursRelative}
+explainer_map = {"IxG": IxG, "Grad": Grad, "Ours": Ours, "OursRelative": OursRelative, "Occlusion": Occlusion}
 """Mapping from explainer name to explainer class."""
 
-OUT_OF_SCOPE = ("Occlusion", "RISE", "LIME", "GCam", "IntGrad", "GB", "DeepLIFT")
+OUT_OF_SCOPE = ("RISE", "LIME", "GCam", "IntGrad", "GB", "DeepLIFT")
 
 
 def get_explainer(model, explainer_name, config_name, **config_overrides):

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define BCOS_ABI_VERSION 11
+#define BCOS_ABI_VERSION 12
 
 enum {
     BCOS_OK = 0,
@@ -829,6 +829,36 @@ typedef struct bcos_agc_tensor {
  * same bits.  BCOS_E_INVAL (before anything is launched) for a NULL array or pointer, ntensors <= 0, units or unit_len <= 0, an
  * overflowing units * unit_len, or a clip_factor / eps that is not finite and positive. */
 int bcos_agc_clip(const bcos_agc_tensor* tensors, int ntensors, float clip_factor, float eps, void* stream);
+
+/* -- Occlusion baseline explainer (ABI v12) ------------------------------------------------------------------------------- */
+/* An occlusion mask is a rectangle: four int32 (r0, r1, c0, c1), rows [r0, r1) x columns [c0, c1) with the half-open slice semantics of
+ * interpretability/explanation_methods/explainers/occlusion.py:46-49, already clipped to the image.  A mask bank is a DEVICE array
+ * [n, 4], 16-byte aligned. */
+
+/* The prepared network input of n occluded copies of ONE image: what bcos_prep_input writes for `img * masks[i]` (occlusion.py:80, then
+ * the 6-channel Normalize of bcosify.py:38-43), bit for bit, without the [n, 6, H, W] masked batch ever being stored.
+ * x: [1,6,H,W] NCHW; rects: device [n,4] (the caller offsets the pointer into a larger bank); out: [n,H,W,Cpad], channels >= 6 zero;
+ * inside rectangle i every channel of copy i is (0 - mean) / std: the mask multiplies the network input BEFORE Normalize.
+ * absmax_out (NULL or [n*H*W]): per-pixel max |out| bit patterns, as bcos_prep_input.  One thread per output pixel, 16-byte stores for
+ * Cpad == 8; the source image is re-read per copy (L2).  64-bit offsets.
+ * BCOS_E_INVAL: a NULL pointer, n / H / W <= 0, Cpad < 6, Cx != 6 or add_inverse != 0 (masking before AddInverse is another operator),
+ * H * W > 2^31 - 1, misaligned rects. */
+int bcos_prep_input_occluded(const float* x, const int32_t* rects, float* out, const float* mean6, const float* std6,
+                             uint32_t* absmax_out, int n, int Cx, int H, int W, int Cpad, int add_inverse, void* stream);
+
+/* The attribution maps of occlusion.py:93-108 from logits that stayed on the device, without the [n_masks, classes, H, W] intermediate:
+ *   out[t, h, w] = sum over m in ascending order of  [(h, w) in rect_m] * d(m, t) / n_part_m,
+ *   d(m, t) = org[c_t] - pert[m, c_t] (clamped at 0 from below when only_positive; a NaN stays NaN), n_part_m = (r1 - r0) * (c1 - c0),
+ *   c_t = targets[t] (device int32 [T]) or t when targets is NULL (then T must equal CL).
+ * org [CL], pert [n, CL], rects device [n, 4], out [T, H, W]; pixels no mask covers get 0.  Everything is fp32: one subtraction, one
+ * correctly rounded division and one addition per covering mask, the additions as ONE chain in ascending m for every element -- no
+ * atomics; the bits do not depend on T, on the launch shape or on how pert was produced.  A target outside [0, CL) yields NaN for its
+ * map (never an out-of-bounds read).  rects_host (NULL or a HOST copy of the bank) is what the call validates, since it never reads
+ * device memory: BCOS_E_INVAL for a rectangle with an empty side (the reference divides 0 by 0 there) or one that leaves the image;
+ * with NULL the caller vouches for the bank (an empty rectangle then contributes nothing).
+ * BCOS_E_INVAL also: a NULL org / pert / rects / out, n / CL / T / H / W <= 0, targets == NULL with T != CL, misaligned rects. */
+int bcos_occlusion_accumulate(const float* org, const float* pert, const int32_t* rects, const int32_t* rects_host,
+                              const int32_t* targets, float* out, int n, int CL, int T, int H, int W, int only_positive, void* stream);
 
 #ifdef __cplusplus
 }
