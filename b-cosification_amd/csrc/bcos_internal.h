@@ -27,10 +27,11 @@ int64_t bcos_option(int option);
 
 struct bcos_tapconv_geom;
 struct bcos_epilogue;
-// narrow-output (Cout <= 8) path, bcos_skinny.hip: 1 = handled, 0 = not applicable, < 0 = error.  decide_ch != NULL: decide only --
-// nothing is launched and *decide_ch receives the channels staged per pass (bcos_tapconv_route_query)
-int bcos_try_skinny(const float* a, const float* wt, const bcos_tapconv_geom& g, const bcos_epilogue& e, int M,
-                    hipStream_t stream, int* decide_ch = nullptr);
+// narrow-output (Cout <= 8) kernel, bcos_skinny.hip.  bcos_skinny_ch_pass decides: the input channels staged per pass if the kernel takes
+// the launch, 0 if it does not (nothing is launched: the dispatcher and bcos_tapconv_route_query ask it).  bcos_skinny_launch launches what
+// bcos_skinny_ch_pass accepted: BCOS_OK or an error code.
+int bcos_skinny_ch_pass(const bcos_tapconv_geom& g, const bcos_epilogue& e);
+int bcos_skinny_launch(const float* a, const float* wt, const bcos_tapconv_geom& g, const bcos_epilogue& e, hipStream_t stream);
 
 // several tap sets over one input (parity classes of a strided gradient) fused into one launch, bcos_skinny.hip
 int bcos_try_skinny_group(const float* a, const float* const* wts, const bcos_tapconv_geom* gs, const bcos_epilogue* es,

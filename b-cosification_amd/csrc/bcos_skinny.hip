@@ -352,16 +352,18 @@ __global__ __launch_bounds__(SK_THREADS) void skinny_group_kernel(const SkGroupA
 
 }  // namespace
 
-// Returns 1 if the launch was handled here, 0 if the caller should use the generic kernel, < 0 on error.
-int bcos_try_skinny(const float* a, const float* wt, const bcos_tapconv_geom& g, const bcos_epilogue& e, int M,
-                    hipStream_t stream, int* decide_ch) {
-    (void)M;
-    if (g.Cout > 8) return 0;
+namespace {
+struct SkPlan { SkArgs args; size_t lds; int64_t blocks; };
+
+// Does the narrow-output kernel take this launch?  If so, plan.args is its descriptor (CH: the channels per pass), with the LDS bytes
+// and the block count of the launch.
+bool skinny_decide(const float* a, const float* wt, const bcos_tapconv_geom& g, const bcos_epilogue& e, SkPlan& plan) {
+    if (g.Cout > 8) return false;
     if (e.bcos_mode != BCOS_NONE || e.bias || e.ch_scale || e.ch_shift || e.relu || e.out2 || e.scale_out ||
         e.norm_out || e.mul2 || e.gate2 || !e.out)
-        return 0;
-    if (g.in_sh != 1 || g.in_sw != 1 || g.dstep_h != 1 || g.dstep_w != 1) return 0;
-    SkArgs p;
+        return false;
+    if (g.in_sh != 1 || g.in_sw != 1 || g.dstep_h != 1 || g.dstep_w != 1) return false;
+    SkArgs& p = plan.args;
     p.a = a; p.wt = wt; p.out = e.out; p.addend = e.addend; p.mul = e.mul;
     p.g = g;
     p.Ktot = g.TH * g.TW * g.C;
@@ -379,20 +381,31 @@ int bcos_try_skinny(const float* a, const float* wt, const bcos_tapconv_geom& g,
         if (need <= 40 * 1024) { p.CH = ch; lds = need; break; }
         if (g.C % (ch / 2) != 0 || (ch / 2) % 4 != 0) break;
     }
-    if (p.CH == 0) return 0;
+    if (p.CH == 0) return false;
     if (lds < (size_t)4 * 4 * 64 * 8 * sizeof(float)) lds = (size_t)4 * 4 * 64 * 8 * sizeof(float);   // reduction buffer
     p.ldw = g.TH * g.TW * p.CH + 4;
     p.ldp = p.CH + 4;
-    const int64_t blocks = (int64_t)g.N * p.tiles_i * p.tiles_j;
-    if (blocks >= ((int64_t)1 << 31)) return 0;
-    if (decide_ch) { *decide_ch = p.CH; return 1; }
+    plan.lds = lds;
+    plan.blocks = (int64_t)g.N * p.tiles_i * p.tiles_j;
+    return plan.blocks < ((int64_t)1 << 31);
+}
+}  // namespace
+
+int bcos_skinny_ch_pass(const bcos_tapconv_geom& g, const bcos_epilogue& e) {
+    SkPlan plan;
+    return skinny_decide(nullptr, nullptr, g, e, plan) ? plan.args.CH : 0;
+}
+
+int bcos_skinny_launch(const float* a, const float* wt, const bcos_tapconv_geom& g, const bcos_epilogue& e, hipStream_t stream) {
+    SkPlan plan;
+    if (!skinny_decide(a, wt, g, e, plan)) return bcos_set_error(BCOS_E_INVAL, "bcos_skinny_launch: not a narrow-output launch");
     static std::atomic<size_t> lds_hw{0};
-    hipError_t err = bcos_ensure_dynamic_lds(reinterpret_cast<const void*>(skinny_kernel), lds, lds_hw);
+    hipError_t err = bcos_ensure_dynamic_lds(reinterpret_cast<const void*>(skinny_kernel), plan.lds, lds_hw);
     if (err != hipSuccess) return bcos_set_hip_error("hipFuncSetAttribute(skinny)", err);
-    hipLaunchKernelGGL(skinny_kernel, dim3((unsigned)blocks), dim3(SK_THREADS), lds, stream, p);
+    hipLaunchKernelGGL(skinny_kernel, dim3((unsigned)plan.blocks), dim3(SK_THREADS), plan.lds, stream, plan.args);
     err = hipGetLastError();
     if (err != hipSuccess) return bcos_set_hip_error("skinny launch", err);
-    return 1;
+    return BCOS_OK;
 }
 
 

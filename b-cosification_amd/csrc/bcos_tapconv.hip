@@ -3182,10 +3182,26 @@ constexpr size_t epilogue_lds() {
     return (size_t)SBM * (SBN + 4) * sizeof(float) + (size_t)BM * 20 + (size_t)BN * 4 + (size_t)BM * 8 + 144;      // (+ the row maxima of the column parts + the per-image range cells)
 }
 
-// which loop a launch_cfg launch instantiates -- the LOOP template argument of its kernel, numbered like BCOS_LOOP_F32 / BCOS_LOOP_BF16X3 /
-// BCOS_LOOP_BF16X3_PRESPLIT of include/bcos_hip.h: the one place that decides it, for the launch and for bcos_tapconv_route_query
-inline int cfg_loop(const KArgs& p) { return p.x3 ? (p.wt3 ? BCOS_LOOP_BF16X3_PRESPLIT : BCOS_LOOP_BF16X3) : BCOS_LOOP_F32; }
-static_assert(BCOS_LOOP_F32 == 0 && BCOS_LOOP_BF16X3 == 1 && BCOS_LOOP_BF16X3_PRESPLIT == 2, "cfg_loop returns the kernel's LOOP argument");
+// The launcher families (launch_cfg / launch_h2 / launch_d / launch_p) and the contraction loop a family's launch runs, numbered like BCOS_LOOP_* of
+// include/bcos_hip.h: the one place that decides it, for launch_cfg (the LOOP template argument of its kernel) and for bcos_tapconv_route_query
+enum : int { BCOS_FAM_CFG, BCOS_FAM_H2, BCOS_FAM_D, BCOS_FAM_P };
+inline int family_loop(int fam, const KArgs& p) {
+    if (fam == BCOS_FAM_CFG) return p.x3 ? (p.wt3 ? BCOS_LOOP_BF16X3_PRESPLIT : BCOS_LOOP_BF16X3) : BCOS_LOOP_F32;
+    return fam == BCOS_FAM_H2 ? BCOS_LOOP_F16X2_REGS : fam == BCOS_FAM_D ? BCOS_LOOP_F16X2_DMA : BCOS_LOOP_F16X2_PATCH;
+}
+static_assert(BCOS_LOOP_F32 == 0 && BCOS_LOOP_BF16X3 == 1 && BCOS_LOOP_BF16X3_PRESPLIT == 2, "family_loop returns the kernel's LOOP argument");
+
+// The launch of every family: raise the kernel's dynamic-LDS limit if this launch needs more than any before it (`lds_hw`: the high-water
+// mark, a static of the caller per kernel instantiation), launch, and turn a HIP error into BCOS_E_LAUNCH
+template <class Kernel>
+int launch_tiles(Kernel k, dim3 grid, size_t lds, hipStream_t stream, const KArgs& p, std::atomic<size_t>& lds_hw) {
+    hipError_t err = bcos_ensure_dynamic_lds(reinterpret_cast<const void*>(k), lds, lds_hw);
+    if (err != hipSuccess) return bcos_set_hip_error("hipFuncSetAttribute", err);
+    hipLaunchKernelGGL(k, grid, dim3(NTHREADS), lds, stream, p);
+    err = hipGetLastError();
+    if (err != hipSuccess) return bcos_set_hip_error("tapconv launch", err);
+    return BCOS_OK;
+}
 
 template <int BM, int BN, int WAVES_M, int WAVES_N>
 int launch_cfg(const KArgs& base, bool norm, hipStream_t stream) {
@@ -3194,29 +3210,19 @@ int launch_cfg(const KArgs& base, bool norm, hipStream_t stream) {
     size_t lds = 2 * (size_t)(BM + BN) * LDS_LD * sizeof(float);
     const size_t lds_epi = epilogue_lds<BM, BN, WAVES_M>();
     if (lds_epi > lds) lds = lds_epi;
-    const dim3 grid((unsigned)(p.n_big + p.n_small), (unsigned)(p.g.groups > 1 ? p.g.groups : 1)), block(NTHREADS);     // y = group
-    hipError_t err;
+    const dim3 grid((unsigned)(p.n_big + p.n_small), (unsigned)(p.g.groups > 1 ? p.g.groups : 1));     // y = group
     const size_t lds_x3 = 2 * 3 * (size_t)(BM + BN) * X3_ROW;
     if (p.x3 && lds_x3 > lds_epi) lds = lds_x3;
     else if (p.x3) lds = lds_epi;
     static std::atomic<size_t> lds_hw[6];           // per kernel instantiation of this tile configuration
-    auto launch = [&](auto k, int which) -> hipError_t {
-        hipError_t e2 = bcos_ensure_dynamic_lds(reinterpret_cast<const void*>(k), lds, lds_hw[which]);
-        if (e2 != hipSuccess) return e2;
-        hipLaunchKernelGGL(k, grid, block, lds, stream, p);
-        return hipSuccess;
-    };
-    const int loop = cfg_loop(p);
-    if (loop == BCOS_LOOP_BF16X3_PRESPLIT) err = norm ? launch(tapconv_kernel<BM, BN, WAVES_M, WAVES_N, true, 2>, 0)
-                                                      : launch(tapconv_kernel<BM, BN, WAVES_M, WAVES_N, false, 2>, 1);
-    else if (loop == BCOS_LOOP_BF16X3) err = norm ? launch(tapconv_kernel<BM, BN, WAVES_M, WAVES_N, true, 1>, 2)
-                                                  : launch(tapconv_kernel<BM, BN, WAVES_M, WAVES_N, false, 1>, 3);
-    else err = norm ? launch(tapconv_kernel<BM, BN, WAVES_M, WAVES_N, true, 0>, 4)
-                    : launch(tapconv_kernel<BM, BN, WAVES_M, WAVES_N, false, 0>, 5);
-    if (err != hipSuccess) return bcos_set_hip_error("hipFuncSetAttribute", err);
-    err = hipGetLastError();
-    if (err != hipSuccess) return bcos_set_hip_error("tapconv launch", err);
-    return BCOS_OK;
+    auto launch = [&](auto k, int which) { return launch_tiles(k, grid, lds, stream, p, lds_hw[which]); };
+    const int loop = family_loop(BCOS_FAM_CFG, p);
+    if (loop == BCOS_LOOP_BF16X3_PRESPLIT) return norm ? launch(tapconv_kernel<BM, BN, WAVES_M, WAVES_N, true, 2>, 0)
+                                                       : launch(tapconv_kernel<BM, BN, WAVES_M, WAVES_N, false, 2>, 1);
+    if (loop == BCOS_LOOP_BF16X3) return norm ? launch(tapconv_kernel<BM, BN, WAVES_M, WAVES_N, true, 1>, 2)
+                                              : launch(tapconv_kernel<BM, BN, WAVES_M, WAVES_N, false, 1>, 3);
+    return norm ? launch(tapconv_kernel<BM, BN, WAVES_M, WAVES_N, true, 0>, 4)
+                : launch(tapconv_kernel<BM, BN, WAVES_M, WAVES_N, false, 0>, 5);
 }
 
 template <int BM, int BN, int WAVES_M, int WAVES_N>
@@ -3236,20 +3242,10 @@ int launch_h2(const KArgs& base, bool norm, hipStream_t stream) {
     if (BMS >= 32 && BN / WNS >= 32 && h2_staging_lds<BMS, BN, WMS, WNS>() > lds) lds = h2_staging_lds<BMS, BN, WMS, WNS>();
     const size_t lds_epi = epilogue_lds<BM, BN, WAVES_M>();
     if (lds_epi > lds) lds = lds_epi;
-    const dim3 grid((unsigned)(p.n_big + p.n_small)), block(NTHREADS);
-    static std::atomic<size_t> lds_hw[2];
-    auto launch = [&](auto k, int which) -> hipError_t {
-        hipError_t e2 = bcos_ensure_dynamic_lds(reinterpret_cast<const void*>(k), lds, lds_hw[which]);
-        if (e2 != hipSuccess) return e2;
-        hipLaunchKernelGGL(k, grid, block, lds, stream, p);
-        return hipSuccess;
-    };
-    hipError_t err = norm ? launch(tapconv_kernel<BM, BN, WAVES_M, WAVES_N, true, 3>, 0)
-                          : launch(tapconv_kernel<BM, BN, WAVES_M, WAVES_N, false, 3>, 1);
-    if (err != hipSuccess) return bcos_set_hip_error("hipFuncSetAttribute", err);
-    err = hipGetLastError();
-    if (err != hipSuccess) return bcos_set_hip_error("tapconv launch", err);
-    return BCOS_OK;
+    const dim3 grid((unsigned)(p.n_big + p.n_small));
+    static std::atomic<size_t> lds_hw[2];           // per kernel instantiation
+    return norm ? launch_tiles(tapconv_kernel<BM, BN, WAVES_M, WAVES_N, true, 3>, grid, lds, stream, p, lds_hw[0])
+                : launch_tiles(tapconv_kernel<BM, BN, WAVES_M, WAVES_N, false, 3>, grid, lds, stream, p, lds_hw[1]);
 }
 
 // split-f16 launches with LDS-DMA staging (tile_body_d): ring + row scales + (channel-chunk-major launches) the tap table
@@ -3267,20 +3263,10 @@ int launch_d(const KArgs& base, bool norm, hipStream_t stream) {
         if (want > lds) lds = want;
     }
     if (const int64_t kb = bcos_option(BCOS_OPT_LDS_MIN_KB)) { if ((size_t)kb * 1024 > lds) lds = (size_t)kb * 1024; }
-    const dim3 grid((unsigned)(p.n_big + p.n_small)), block(NTHREADS);
-    static std::atomic<size_t> lds_hw[2];
-    auto launch = [&](auto k, int which) -> hipError_t {
-        hipError_t e2 = bcos_ensure_dynamic_lds(reinterpret_cast<const void*>(k), lds, lds_hw[which]);
-        if (e2 != hipSuccess) return e2;
-        hipLaunchKernelGGL(k, grid, block, lds, stream, p);
-        return hipSuccess;
-    };
-    hipError_t err = norm ? launch(tapconv_kernel<BM, BN, WAVES_M, WAVES_N, true, 4>, 0)
-                          : launch(tapconv_kernel<BM, BN, WAVES_M, WAVES_N, false, 4>, 1);
-    if (err != hipSuccess) return bcos_set_hip_error("hipFuncSetAttribute", err);
-    err = hipGetLastError();
-    if (err != hipSuccess) return bcos_set_hip_error("tapconv launch", err);
-    return BCOS_OK;
+    const dim3 grid((unsigned)(p.n_big + p.n_small));
+    static std::atomic<size_t> lds_hw[2];           // per kernel instantiation
+    return norm ? launch_tiles(tapconv_kernel<BM, BN, WAVES_M, WAVES_N, true, 4>, grid, lds, stream, p, lds_hw[0])
+                : launch_tiles(tapconv_kernel<BM, BN, WAVES_M, WAVES_N, false, 4>, grid, lds, stream, p, lds_hw[1]);
 }
 
 // split-f16 launches over an LDS-resident input patch (tile_body_p); every tile has BM rows
@@ -3306,20 +3292,10 @@ int launch_p(const KArgs& base, bool norm, hipStream_t stream) {
     p.lvl_off = (int)lds;              // row levels + level mask of a tile (tile_body_p), kept across the tile's epilogues
     lds += BM + 16;
     if (const int64_t kb = bcos_option(BCOS_OPT_LDS_MIN_KB)) { if ((size_t)kb * 1024 > lds) lds = (size_t)kb * 1024; }
-    const dim3 grid((unsigned)p.n_big), block(NTHREADS);
-    static std::atomic<size_t> lds_hw[2];
-    auto launch = [&](auto k, int which) -> hipError_t {
-        hipError_t e2 = bcos_ensure_dynamic_lds(reinterpret_cast<const void*>(k), lds, lds_hw[which]);
-        if (e2 != hipSuccess) return e2;
-        hipLaunchKernelGGL(k, grid, block, lds, stream, p);
-        return hipSuccess;
-    };
-    hipError_t err = norm ? launch(tappatch_kernel<BM, BN, WAVES_M, WAVES_N, true, NI, PXL, NTAPS, T2BW>, 0)
-                          : launch(tappatch_kernel<BM, BN, WAVES_M, WAVES_N, false, NI, PXL, NTAPS, T2BW>, 1);
-    if (err != hipSuccess) return bcos_set_hip_error("hipFuncSetAttribute", err);
-    err = hipGetLastError();
-    if (err != hipSuccess) return bcos_set_hip_error("tapconv launch", err);
-    return BCOS_OK;
+    const dim3 grid((unsigned)p.n_big);
+    static std::atomic<size_t> lds_hw[2];           // per kernel instantiation
+    return norm ? launch_tiles(tappatch_kernel<BM, BN, WAVES_M, WAVES_N, true, NI, PXL, NTAPS, T2BW>, grid, lds, stream, p, lds_hw[0])
+                : launch_tiles(tappatch_kernel<BM, BN, WAVES_M, WAVES_N, false, NI, PXL, NTAPS, T2BW>, grid, lds, stream, p, lds_hw[1]);
 }
 
 // Does the input patch of every BM-row tile of the launch fit `px` pixels?  Upper bound over the tile positions: a tile touches
@@ -3365,10 +3341,9 @@ extern "C" int BCOS_PH_NAME(BCOS_TAPCONV_PART)(unsigned long long* out) {
 #endif
 #define BCOS_TC_IN(k) (BCOS_TAPCONV_PART == -1 || BCOS_TAPCONV_PART == (k))
 #define BCOS_TC_LAUNCHER(name) __attribute__((visibility("hidden"))) int name(const void* kargs, int norm, hipStream_t s)
-// every tile launcher, once: X(name, launcher family = which loop it instantiates, tile rows, tile columns).  The list declares the launchers, numbers them (the route ids of
+// every tile launcher, once: X(name, launcher family (BCOS_FAM_*: which loop it instantiates, family_loop), tile rows, tile columns).  The list declares the launchers, numbers them (the route ids of
 // bcos_tapconv_route_query, the narrow-output kernel of bcos_skinny.hip last) and fills the table the dispatcher launches through;
 // BCOS_TC_DEFINE refuses a launcher that is not in it, and one that is listed without a definition does not link
-enum : int { BCOS_FAM_CFG, BCOS_FAM_H2, BCOS_FAM_D, BCOS_FAM_P };      // launch_cfg / launch_h2 / launch_d / launch_p
 #define BCOS_TC_ROUTES(X) \
     X(cfg_128x128, BCOS_FAM_CFG, 128, 128) \
     X(cfg_128x64, BCOS_FAM_CFG, 128, 64) \
@@ -3937,81 +3912,32 @@ extern "C" int bcos_tapconv_presplit(const float* a, const float* wt, const void
     return bcos_tapconv_ops(&o, geom, epi, stream);
 }
 
+// ---- the dispatch of bcos_tapconv_ops, in stages: validate -> (batch chunks) -> resolve -> choose_route -> launch_route.  The two queries
+// (bcos_tapconv_fuses_image_range, bcos_tapconv_route_query) run the same stages and stop ahead of the launch.
 namespace {
-thread_local bool t_query_image_range = false;
-thread_local bcos_tapconv_route* t_query_route = nullptr;       // bcos_tapconv_route_query: where the dispatch reports instead of launching
-
 struct RouteEntry { const char* name; int fam, bm, bn; int (*launch)(const void*, int, hipStream_t); };
 #define BCOS_TC_X_ROW(name, fam, bm, bn) {#name, fam, bm, bn, bcos_tc_##name},
 const RouteEntry ROUTES[ROUTE_COUNT] = {BCOS_TC_ROUTES(BCOS_TC_X_ROW) {"skinny", -1, 0, 0, nullptr}};
+struct Route { int id, ch_pass; };      // ROUTE_*; ch_pass: input channels per pass of ROUTE_skinny, 0 otherwise
+struct Call { bcos_operands ops; bcos_tapconv_geom g; bcos_epilogue e; };
 
-// the ONE place a tile launcher is entered from: a query records the route and stops here
-inline int route_go(int id, const KArgs& p, bool norm, hipStream_t s) {
-    if (bcos_tapconv_route* r = t_query_route) {
-        const int fam = ROUTES[id].fam;
-        r->route = id;
-        r->epi_kind = p.epi_kind;
-        r->norm = norm ? 1 : 0;
-        r->loop = fam == BCOS_FAM_CFG ? cfg_loop(p)      // (what launch_cfg asks itself)
-                  : fam == BCOS_FAM_H2 ? BCOS_LOOP_F16X2_REGS : fam == BCOS_FAM_D ? BCOS_LOOP_F16X2_DMA : BCOS_LOOP_F16X2_PATCH;
-        r->bm = ROUTES[id].bm;
-        r->bn = ROUTES[id].bn;
-        r->chunks = 1;
-        r->ch_pass = 0;
-        return BCOS_OK;
-    }
-    return ROUTES[id].launch(&p, norm ? 1 : 0, s);
-}
-#define BCOS_TC_GO(name) route_go(ROUTE_##name, p, norm, s)
-}  // namespace
+inline int contraction_mode(const bcos_operands& o) { return o.contraction == BCOS_CONTRACT_DEFAULT ? g_contraction_mode.load(std::memory_order_relaxed) : o.contraction - 1; }
 
-extern "C" int bcos_tapconv_ops(const bcos_operands* ops, const bcos_tapconv_geom* geom, const bcos_epilogue* epi, void* stream);
-
-// 1: a bcos_tapconv_ops call with these arguments folds the per-image range of its out_absmax into bcos_epilogue.out_imgmax / out_imgmin_c
-// itself; 0: it does not (general epilogue, depth-to-space or grouped launch, fewer than 19 rows per image, no out_absmax) and rejects
-// the two fields; < 0: the arguments are invalid anyway.  Nothing is launched: the call walks bcos_tapconv_ops' own validation and
-// epilogue selection and stops ahead of the dispatch.
-extern "C" int bcos_tapconv_fuses_image_range(const bcos_operands* ops, const bcos_tapconv_geom* geom, const bcos_epilogue* epi) {
-    t_query_image_range = true;
-    const int rc = bcos_tapconv_ops(ops, geom, epi, nullptr);
-    t_query_image_range = false;
-    return rc;
-}
-
-extern "C" int bcos_tapconv_route_query(const bcos_operands* ops, const bcos_tapconv_geom* geom, const bcos_epilogue* epi, bcos_tapconv_route* out) {
-    if (!out) return bcos_set_error(BCOS_E_INVAL, "bcos_tapconv_route_query: NULL result");
-    *out = bcos_tapconv_route{-1, 0, 0, 0, 0, 0, 0, 0};
-    t_query_route = out;
-    const int rc = bcos_tapconv_ops(ops, geom, epi, nullptr);
-    t_query_route = nullptr;
-    return rc;
-}
-
-extern "C" const char* bcos_tapconv_route_name(int route) { return route >= 0 && route < ROUTE_COUNT ? ROUTES[route].name : nullptr; }
-extern "C" int bcos_tapconv_route_count(void) { return ROUTE_COUNT; }
-extern "C" int bcos_tapconv_epilogue_kinds(void) { return N_EPI_KINDS; }
-
-extern "C" int bcos_tapconv_ops(const bcos_operands* ops, const bcos_tapconv_geom* geom, const bcos_epilogue* epi, void* stream) {
+// stage 1: the argument checks.  *gn receives the geometry with its default pitches filled in.
+int validate(const bcos_operands* ops, const bcos_tapconv_geom* geom, const bcos_epilogue* epi, bcos_tapconv_geom* gn) {
     if (!ops || !geom || !epi) return bcos_set_error(BCOS_E_INVAL, "bcos_tapconv: NULL argument");
-    const float* a = ops->a;
-    const float* wt = ops->wt;
-    const void* wt3 = ops->wt_bf16x3;
-    if (!a || !wt) return bcos_set_error(BCOS_E_INVAL, "bcos_tapconv: NULL operand");
+    if (!ops->a || !ops->wt) return bcos_set_error(BCOS_E_INVAL, "bcos_tapconv: NULL operand");
     if (ops->contraction < 0 || ops->contraction > BCOS_CONTRACT_F16X2)
         return bcos_set_error(BCOS_E_INVAL, "bcos_tapconv: bad contraction selector");
-    const int mode = ops->contraction == BCOS_CONTRACT_DEFAULT ? g_contraction_mode.load(std::memory_order_relaxed)
-                                                               : ops->contraction - 1;
     const bcos_tapconv_geom& g = *geom;
     if (g.N <= 0 || g.H <= 0 || g.W <= 0 || g.C <= 0 || g.P <= 0 || g.Q <= 0 || g.TH <= 0 || g.TW <= 0 ||
         g.Cout <= 0 || g.OH <= 0 || g.OW <= 0)
         return bcos_set_error(BCOS_E_INVAL, "bcos_tapconv: non-positive dimension");
     if (g.C % 4 != 0) return bcos_set_error(BCOS_E_INVAL, "bcos_tapconv: C must be a multiple of 4");
-    if ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(wt)) & 15)
+    if ((reinterpret_cast<uintptr_t>(ops->a) | reinterpret_cast<uintptr_t>(ops->wt)) & 15)
         return bcos_set_error(BCOS_E_INVAL, "bcos_tapconv: operands must be 16-byte aligned");
-    const int64_t M64 = (int64_t)g.N * g.P * g.Q;
-    if (M64 >= (int64_t)1 << 31) return bcos_set_error(BCOS_E_NOSUP, "bcos_tapconv: more than 2^31 rows");
-    if (!epi->out && !epi->out2 && !epi->scale_out)
-        return bcos_set_error(BCOS_E_INVAL, "bcos_tapconv: no output buffer");
+    if ((int64_t)g.N * g.P * g.Q >= (int64_t)1 << 31) return bcos_set_error(BCOS_E_NOSUP, "bcos_tapconv: more than 2^31 rows");
+    if (!epi->out && !epi->out2 && !epi->scale_out) return bcos_set_error(BCOS_E_INVAL, "bcos_tapconv: no output buffer");
     if (epi->max_out < 0) return bcos_set_error(BCOS_E_INVAL, "bcos_tapconv: negative max_out");
     if ((epi->flags & BCOS_EPI_MUL_FROM_ACT) && (!epi->mul || !epi->mul_norm || (epi->flags & BCOS_EPI_GATE2_FROM_MUL)))
         return bcos_set_error(BCOS_E_INVAL, "bcos_tapconv: BCOS_EPI_MUL_FROM_ACT needs mul and mul_norm and excludes GATE2_FROM_MUL");
@@ -4032,8 +3958,7 @@ extern "C" int bcos_tapconv_ops(const bcos_operands* ops, const bcos_tapconv_geo
         return bcos_set_error(BCOS_E_INVAL, "bcos_tapconv: addend_sub > 1 needs an addend and a plain gradient launch (bcos_mode BCOS_NONE, "
                                             "no out_cgroup, no groups)");
     // the last row/col written must be inside the output tensor
-    if ((g.P - 1) * g.out_sh + g.out_h0 >= g.OH || (g.Q - 1) * g.out_sw + g.out_w0 >= g.OW || g.out_h0 < 0 ||
-        g.out_w0 < 0)
+    if ((g.P - 1) * g.out_sh + g.out_h0 >= g.OH || (g.Q - 1) * g.out_sw + g.out_w0 >= g.OW || g.out_h0 < 0 || g.out_w0 < 0)
         return bcos_set_error(BCOS_E_INVAL, "bcos_tapconv: output mapping outside [OH,OW]");
     const int G = g.groups > 1 ? g.groups : 1;
     if (g.groups < 0 || g.groups > 65535) return bcos_set_error(BCOS_E_INVAL, "bcos_tapconv: bad group count");
@@ -4050,21 +3975,140 @@ extern "C" int bcos_tapconv_ops(const bcos_operands* ops, const bcos_tapconv_geo
             return bcos_set_error(BCOS_E_NOSUP, "bcos_tapconv: out_cgroup launches are plain gradient launches (addend / mul / mul2 / "
                                                 "gate2 / out / out2 only)");
     }
-
-    KArgs p;
-    p.a = a;
-    p.wt = wt;
-    p.g = g;
-    if (p.g.a_pitch == 0) p.g.a_pitch = G * g.C;
-    if (p.g.out_pitch == 0) p.g.out_pitch = g.out_cgroup > 0 ? g.out_cgroup : G * g.Cout;
-    if (p.g.norm_pitch == 0) p.g.norm_pitch = G;
-    if (p.g.a_pitch % 4 != 0 || p.g.a_pitch < G * g.C) return bcos_set_error(BCOS_E_INVAL, "bcos_tapconv: bad a_pitch");
-    if (epi->max_out > 1 && g.out_pitch == 0) p.g.out_pitch = g.Cout / epi->max_out;
-    if (g.out_cgroup == 0 && p.g.out_pitch < G * g.Cout / (epi->max_out > 1 ? epi->max_out : 1))
+    *gn = g;
+    if (gn->a_pitch == 0) gn->a_pitch = G * g.C;
+    if (gn->out_pitch == 0) gn->out_pitch = g.out_cgroup > 0 ? g.out_cgroup : G * g.Cout;
+    if (gn->norm_pitch == 0) gn->norm_pitch = G;
+    if (gn->a_pitch % 4 != 0 || gn->a_pitch < G * g.C) return bcos_set_error(BCOS_E_INVAL, "bcos_tapconv: bad a_pitch");
+    if (epi->max_out > 1 && g.out_pitch == 0) gn->out_pitch = g.Cout / epi->max_out;
+    if (g.out_cgroup == 0 && gn->out_pitch < G * g.Cout / (epi->max_out > 1 ? epi->max_out : 1))
         return bcos_set_error(BCOS_E_INVAL, "bcos_tapconv: bad out_pitch");
-    if (p.g.norm_pitch < G) return bcos_set_error(BCOS_E_INVAL, "bcos_tapconv: norm_pitch smaller than the group count");
-    p.e = *epi;
-    p.M = (int)M64;
+    if (gn->norm_pitch < G) return bcos_set_error(BCOS_E_INVAL, "bcos_tapconv: norm_pitch smaller than the group count");
+    return BCOS_OK;
+}
+
+// How many images of a validated call go into one launch (g.N: all of them).  The split-bf16 path addresses its operands through
+// 32-bit buffer offsets: keep each launch below 2 GiB of A by splitting the batch (every tensor of the call is per-image separable);
+// a call that cannot be split falls back to fp32 MFMA in select_operands.
+int images_per_launch(const bcos_operands& ops, const bcos_tapconv_geom& g) {
+    const int G = g.groups > 1 ? g.groups : 1, Ktot = g.TH * g.TW * g.C;
+    const int64_t img_bytes = (int64_t)g.H * g.W * g.a_pitch * 4, a_bytes = img_bytes * g.N, wt_bytes = (int64_t)G * g.Cout * Ktot * 4;
+    // (BCOS_OPT_SPLIT_LIMIT: tests lower the chunking threshold to drive this path with small tensors)
+    const int64_t chunk_lim = bcos_option(BCOS_OPT_SPLIT_LIMIT);
+    const bool split = contraction_mode(ops) >= 1 && a_bytes >= chunk_lim && g.N > 1 && img_bytes < chunk_lim && wt_bytes < ((int64_t)1 << 31);
+    return split ? (int)((chunk_lim - 1) / img_bytes) : g.N;
+}
+
+// images [n0, n0 + per) of a call (fewer in the last chunk) as a call of their own: every per-image pointer moved to image n0
+Call chunk_of(const bcos_operands& ops, const bcos_tapconv_geom& g, const bcos_epilogue& epi, int n0, int per) {
+    Call c = {ops, g, epi};
+    bcos_epilogue& e2 = c.e;
+    c.g.N = g.N - n0 < per ? g.N - n0 : per;
+    const int64_t opix = (int64_t)n0 * g.OH * g.OW;
+    const float** cin[] = {&e2.addend, &e2.mul, &e2.mul2, &e2.gate2, &e2.relu_gate, &e2.rowadd};      // indexed like out
+    for (const float** q : cin) if (*q) *q += opix * g.out_pitch;
+    if (const int sb = e2.addend_sub; e2.addend && sb > 1)      // subsampled addend: its own image size
+        e2.addend = epi.addend + (int64_t)n0 * ((g.OH + sb - 1) / sb) * ((g.OW + sb - 1) / sb) * g.out_pitch;
+    float** cout[] = {&e2.out, &e2.out2, &e2.scale_out};
+    for (float** q : cout) if (*q) *q += opix * g.out_pitch;
+    if (e2.norm_out) e2.norm_out += opix * g.norm_pitch;
+    const float** cpx[] = {&e2.mul_norm, &e2.row_scale, &e2.a_sumsq, &e2.rowadd_scale};      // one value per output pixel
+    for (const float** q : cpx) if (*q) *q += opix;
+    if (e2.out_absmax) e2.out_absmax += opix;
+    if (e2.out2_absmax) e2.out2_absmax += opix;
+    if (e2.out_imgmax) e2.out_imgmax += n0;
+    if (e2.out_imgmin_c) e2.out_imgmin_c += n0;
+    bcos_operands& o2 = c.ops;
+    o2.a = ops.a + (int64_t)n0 * g.H * g.W * g.a_pitch;
+    if (o2.a_absmax) o2.a_absmax += (int64_t)n0 * g.H * g.W;
+    if (o2.a_imgmax) o2.a_imgmax += n0;          // (per-image maxima are indexed by the chunk's local image index)
+    if (o2.a_imgmin) o2.a_imgmin += n0;
+    if (o2.a_imgmin_c) o2.a_imgmin_c += n0;
+    return c;
+}
+
+// resolve, part 1: the contraction loop's operands -- x3, the pre-split weight image, the split-f16 decision (p.h2 and its side tensors) -- and the 2 GiB limits
+void select_operands(const bcos_operands& ops, KArgs& p) {
+    const bcos_tapconv_geom& g = p.g;
+    const int mode = contraction_mode(ops), G = g.groups > 1 ? g.groups : 1;
+    const int64_t a_bytes = (int64_t)g.H * g.W * g.a_pitch * 4 * g.N, wt_bytes = (int64_t)G * g.Cout * p.Ktot * 4;
+    const int64_t lim = (int64_t)1 << 31;
+    p.x3 = (mode >= 1 && a_bytes < lim && wt_bytes < lim) ? 1 : 0;
+    p.a_bytes = (unsigned)(a_bytes < lim ? a_bytes : 0);
+    p.wt_bytes = (unsigned)(wt_bytes < lim ? wt_bytes : 0);
+    const int64_t w3b = split_bytes(G * g.Cout, p.Ktot);
+    // (grouped launches index the image by global weight row: a group's rows must start on a 32-row fragment tile)
+    const bool unit_w = (p.e.flags & BCOS_EPI_UNIT_NORM_W) != 0;     // norms come from the fp32 weight rows in the staging registers
+    const void* wt3 = ops.wt_bf16x3;
+    p.wt3 = (p.x3 && !unit_w && wt3 && w3b < lim && !(reinterpret_cast<uintptr_t>(wt3) & 15) && (G == 1 || g.Cout % 32 == 0)) ? wt3 : nullptr;
+    p.wt3_bytes = (unsigned)(w3b < lim ? w3b : 0);
+    p.h2 = 0;
+    p.a_absmax = p.a_imgmax = p.a_imgmin = p.a_imgmin_c = nullptr;
+    p.wt2 = nullptr, p.wt2_cinv = nullptr;
+    p.absmax_bytes = p.wt2_bytes = 0;
+    const int64_t w2b = h2_image_bytes(g.Cout, p.Ktot), pixb = (int64_t)g.N * g.H * g.W * 4;
+    // below K = 256 a launch is HBM-bound and the bf16x3 loop (no operand maxima to produce) is as fast, unless the caller
+    // insists on f16x2; at K = 256 the six bf16 products still occupy a third of the SIMD cycles (14^2 layers of ResNet-50:
+    // -12 % per launch with three f16 products).  The stem's K is all taps over 8 channels: compute-bound at any K.
+    const bool h2_pays = p.Ktot >= 256 || (g.C <= 16 && p.Ktot >= 128) || ops.contraction == BCOS_CONTRACT_F16X2;
+    if (mode == 2 && G == 1 && h2_pays && !unit_w && p.x3 && ops.a_absmax && ops.wt_f16x2 && w2b < lim && pixb < lim &&
+        !(reinterpret_cast<uintptr_t>(ops.wt_f16x2) & 15)) {
+        p.h2 = 1;
+        p.a_absmax = ops.a_absmax;
+        // BCOS_OPT_PATCH = 0 (development / test switch): no per-image range, i.e. per-row scales everywhere -- the per-tap loops as they were
+        if (bcos_option(BCOS_OPT_PATCH) != 0) {
+            p.a_imgmax = ops.a_imgmax;
+            p.a_imgmin = ops.a_imgmax ? ops.a_imgmin : nullptr;
+            p.a_imgmin_c = (ops.a_imgmax && !ops.a_imgmin) ? ops.a_imgmin_c : nullptr;
+        }
+        p.absmax_bytes = (unsigned)pixb;
+        p.wt2 = ops.wt_f16x2;
+        p.wt2_bytes = (unsigned)w2b;
+        p.wt2_cinv = reinterpret_cast<const float*>(static_cast<const char*>(ops.wt_f16x2) + w2b);
+    }
+}
+
+// resolve, part 2: the specialised epilogue (tile_epilogue_fast) when the launch's feature set is one of the compiled kinds; sets p.epi_kind / p.out_bytes
+void select_epilogue_kind(KArgs& p) {
+    const bcos_tapconv_geom& g = p.g;
+    const bcos_epilogue& e = p.e;
+    p.epi_kind = 0, p.out_bytes = 0;
+    const int64_t obytes = (int64_t)g.N * g.OH * g.OW * g.out_pitch * 4;
+    const bool norm_l = e.bcos_mode != BCOS_NONE;
+    const bool off = bcos_option(BCOS_OPT_EPI_GENERIC) != 0;                // development / test switch
+    // (a row_scale rides in the inverse operand scale of the split-f16 loops; the other loops carry it through the general epilogue)
+    bool ok = !off && p.vec_ok && g.Cout % 4 == 0 && obytes < ((int64_t)1 << 31) && e.max_out <= 1 && e.out != nullptr && !e.col_scale && !(e.flags & BCOS_EPI_UNIT_NORM_W) &&
+              (!e.row_scale || p.h2) &&
+              !e.gate2 && !e.relu_gate && !(e.flags & (BCOS_EPI_NORM_ONLY | BCOS_EPI_FORCE_POW)) &&
+              ((reinterpret_cast<uintptr_t>(e.bias) | reinterpret_cast<uintptr_t>(e.ch_scale) | reinterpret_cast<uintptr_t>(e.ch_shift)) & 15) == 0;
+    int ef = 0;
+    if (norm_l) {
+        ok = ok && e.b == 2.0f && e.relu >= 0 && e.relu <= 2 && !e.mul && !e.mul2 && !e.out2 && !e.out2_absmax &&
+             !(e.flags & BCOS_EPI_MUL_FROM_ACT);
+        ef = (e.addend ? EF_ADDEND : 0) | (e.relu == 1 ? EF_RELU : 0) | (e.relu == 2 ? EF_GELU : 0) | (e.scale_out ? EF_SCALE_OUT : 0);
+    } else {
+        ok = ok && e.relu == 0 && !e.ch_scale && !e.ch_shift && !e.scale_out && (!e.mul2 || e.out2) &&
+             (!e.out2 || e.mul) && (!e.out2_absmax || e.out2);
+        // out2 is either ungated or gated by the low bit of mul (BCOS_EPI_GATE2_FROM_MUL): both are what the kinds compute
+        ef = (e.addend ? EF_ADDEND : 0) | (e.mul ? EF_MUL : 0) | (e.out2 ? EF_OUT2 : 0) | (e.mul2 ? EF_MUL2 : 0) |
+             ((e.flags & BCOS_EPI_MUL_FROM_ACT) ? EF_MULACT : 0) | (e.rowadd ? (EF_ROWADD | EF_ADDEND) : 0);
+        if (e.rowadd) ok = ok && e.rowadd_scale && e.addend_sub <= 1 && !(reinterpret_cast<uintptr_t>(e.rowadd) & 15) && g.out_cgroup == 0;
+        if (e.flags & BCOS_EPI_MUL_FROM_ACT)
+            ok = ok && ((reinterpret_cast<uintptr_t>(e.mul_csc) | reinterpret_cast<uintptr_t>(e.mul_csh)) & 15) == 0;
+    }
+    if (!ok) return;
+    const int* kinds = norm_l ? EPI_KINDS_FWD : EPI_KINDS_BWD;
+    for (int k = 0; k < N_EPI_KINDS; ++k)
+        if (kinds[k] == ef) { p.epi_kind = k + 1; p.out_bytes = (unsigned)obytes; break; }
+}
+
+// stage 2: the launch descriptor of one validated call (a chunk of it).  *fuses: does the launch fold the per-image range of its
+// out_absmax into out_imgmax / out_imgmin_c -- what bcos_tapconv_fuses_image_range answers, ahead of plan_launch's check of the pair.
+int resolve(const Call& c, KArgs& p, bool* fuses) {
+    const bcos_tapconv_geom& g = c.g;
+    const bcos_epilogue& e = c.e;
+    p.a = c.ops.a; p.wt = c.ops.wt; p.g = g; p.e = e;
+    p.M = g.N * g.P * g.Q;
     p.PQ = g.P * g.Q;
     p.Ktot = g.TH * g.TW * g.C;
     p.cpt = g.C / 4;
@@ -4072,164 +4116,47 @@ extern "C" int bcos_tapconv_ops(const bcos_operands* ops, const bcos_tapconv_geo
     p.nk = (p.nchunks + 7) / 8;
     p.tiles_n = p.n_big = p.n_small = p.rows_big = 0;
     p.uniform_tap = (g.C % BK == 0) ? 1 : 0;
-    p.x3 = mode >= 1 ? 1 : 0;
-    p.h2 = 0;
-    p.a_absmax = nullptr;
-    p.a_imgmax = nullptr;
-    p.a_imgmin = nullptr;
-    p.a_imgmin_c = nullptr;
     p.lvl_off = 0;
     p.lvl_on = bcos_option(BCOS_OPT_PATCH_LEVELS) != 0;
     p.t2_bw = p.t2_nbx = p.t2_nb = p.t2_rows = 0;
-    p.absmax_bytes = 0;
-    p.wt2 = nullptr;
-    p.wt2_bytes = 0;
-    p.wt2_cinv = nullptr;
-    {   // the split-bf16 path addresses its operands through 32-bit buffer offsets: keep each launch below 2 GiB of A
-        // by splitting the batch (every tensor of the call is per-image separable); fall back to fp32 MFMA otherwise
-        const int64_t img_bytes = (int64_t)g.H * g.W * p.g.a_pitch * 4;
-        const int64_t a_bytes = img_bytes * g.N, wt_bytes = (int64_t)G * g.Cout * p.Ktot * 4;
-        const int64_t lim = (int64_t)1 << 31;
-        // (BCOS_OPT_SPLIT_LIMIT: tests lower the chunking threshold to drive this path with small tensors)
-        const int64_t chunk_lim = bcos_option(BCOS_OPT_SPLIT_LIMIT);
-        if (p.x3 && a_bytes >= chunk_lim && g.N > 1 && img_bytes < chunk_lim && wt_bytes < lim) {
-            const int per = (int)((chunk_lim - 1) / img_bytes);
-            for (int n0 = 0; n0 < g.N; n0 += per) {
-                bcos_tapconv_geom g2 = p.g;
-                bcos_epilogue e2 = *epi;
-                g2.N = g.N - n0 < per ? g.N - n0 : per;
-                const int64_t opix = (int64_t)n0 * g.OH * g.OW;
-                const float** cin[] = {&e2.addend, &e2.mul, &e2.mul2, &e2.gate2, &e2.relu_gate};
-                for (const float** q : cin) if (*q) *q += opix * p.g.out_pitch;
-                if (e2.addend && e2.addend_sub > 1) {      // subsampled addend: its own image size
-                    const int sb = e2.addend_sub;
-                    e2.addend = epi->addend + (int64_t)n0 * ((g.OH + sb - 1) / sb) * ((g.OW + sb - 1) / sb) * p.g.out_pitch;
-                }
-                float** cout[] = {&e2.out, &e2.out2, &e2.scale_out};
-                for (float** q : cout) if (*q) *q += opix * p.g.out_pitch;
-                if (e2.norm_out) e2.norm_out += opix * p.g.norm_pitch;
-                if (e2.mul_norm) e2.mul_norm += opix;
-                if (e2.row_scale) e2.row_scale += opix;
-                if (e2.a_sumsq) e2.a_sumsq += opix;
-                if (e2.out_absmax) e2.out_absmax += opix;
-                if (e2.out2_absmax) e2.out2_absmax += opix;
-                if (e2.out_imgmax) e2.out_imgmax += n0;
-                if (e2.out_imgmin_c) e2.out_imgmin_c += n0;
-                if (e2.rowadd) e2.rowadd += opix * p.g.out_pitch;
-                if (e2.rowadd_scale) e2.rowadd_scale += opix;
-                bcos_operands o2 = *ops;
-                o2.a = a + (int64_t)n0 * g.H * g.W * p.g.a_pitch;
-                if (o2.a_absmax) o2.a_absmax += (int64_t)n0 * g.H * g.W;
-                if (o2.a_imgmax) o2.a_imgmax += n0;          // (per-image maxima are indexed by the chunk's local image index)
-                if (o2.a_imgmin) o2.a_imgmin += n0;
-                if (o2.a_imgmin_c) o2.a_imgmin_c += n0;
-                const int rc = bcos_tapconv_ops(&o2, &g2, &e2, stream);
-                if (rc != BCOS_OK) return rc;
-                if (t_query_route) { t_query_route->chunks = (g.N + per - 1) / per; return BCOS_OK; }      // (the first chunk's route)
-            }
-            return BCOS_OK;
-        }
-        if (a_bytes >= lim || wt_bytes >= lim) p.x3 = 0;
-        p.a_bytes = (unsigned)(a_bytes < lim ? a_bytes : 0);
-        p.wt_bytes = (unsigned)(wt_bytes < lim ? wt_bytes : 0);
-        const int64_t w3b = split_bytes(G * g.Cout, p.Ktot);
-        // (grouped launches index the image by global weight row: a group's rows must start on a 32-row fragment tile)
-        const bool unit_w = (epi->flags & BCOS_EPI_UNIT_NORM_W) != 0;     // norms come from the fp32 weight rows in the staging registers
-        p.wt3 = (p.x3 && !unit_w && wt3 && w3b < lim && !(reinterpret_cast<uintptr_t>(wt3) & 15) && (G == 1 || g.Cout % 32 == 0)) ? wt3 : nullptr;
-        p.wt3_bytes = (unsigned)(w3b < lim ? w3b : 0);
-        const int64_t w2b = h2_image_bytes(g.Cout, p.Ktot), pixb = (int64_t)g.N * g.H * g.W * 4;
-        // below K = 256 a launch is HBM-bound and the bf16x3 loop (no operand maxima to produce) is as fast, unless the caller
-        // insists on f16x2; at K = 256 the six bf16 products still occupy a third of the SIMD cycles (14^2 layers of ResNet-50:
-        // -12 % per launch with three f16 products).  The stem's K is all taps over 8 channels: compute-bound at any K.
-        const bool h2_pays = p.Ktot >= 256 || (g.C <= 16 && p.Ktot >= 128) || ops->contraction == BCOS_CONTRACT_F16X2;
-        if (mode == 2 && G == 1 && h2_pays && !unit_w && p.x3 && ops->a_absmax && ops->wt_f16x2 && w2b < lim && pixb < lim &&
-            !(reinterpret_cast<uintptr_t>(ops->wt_f16x2) & 15)) {
-            p.h2 = 1;
-            p.a_absmax = ops->a_absmax;
-            p.a_imgmax = ops->a_imgmax;
-            p.a_imgmin = ops->a_imgmax ? ops->a_imgmin : nullptr;
-            p.a_imgmin_c = (ops->a_imgmax && !ops->a_imgmin) ? ops->a_imgmin_c : nullptr;
-            p.absmax_bytes = (unsigned)pixb;
-            p.wt2 = ops->wt_f16x2;
-            p.wt2_bytes = (unsigned)w2b;
-            p.wt2_cinv = reinterpret_cast<const float*>(static_cast<const char*>(ops->wt_f16x2) + w2b);
-        }
-    }
-    {
-        uintptr_t bits = 0;
-        const void* ptrs[] = {epi->addend, epi->mul, epi->mul2, epi->gate2, epi->relu_gate, epi->out, epi->out2, epi->scale_out};
-        for (const void* q : ptrs) bits |= reinterpret_cast<uintptr_t>(q);
-        p.vec_ok = ((bits & 15) == 0 && p.g.out_pitch % 4 == 0) ? 1 : 0;
-        if (g.out_cgroup > 0 && !p.vec_ok)
-            return bcos_set_error(BCOS_E_INVAL, "bcos_tapconv: out_cgroup needs 16-byte addressable epilogue tensors");
-    }
-    {   // specialised epilogue (tile_epilogue_fast) when the launch's feature set is one of the compiled kinds
-        p.epi_kind = 0;
-        p.out_bytes = 0;
-        const bcos_epilogue& e = *epi;
-        const int64_t obytes = (int64_t)g.N * g.OH * g.OW * p.g.out_pitch * 4;
-        const bool norm_l = e.bcos_mode != BCOS_NONE;
-        const bool off = bcos_option(BCOS_OPT_EPI_GENERIC) != 0;                // development / test switch
-        // (a row_scale rides in the inverse operand scale of the split-f16 loops; the other loops carry it through the general epilogue)
-        bool ok = !off && p.vec_ok && g.Cout % 4 == 0 && obytes < ((int64_t)1 << 31) && e.max_out <= 1 && e.out != nullptr && !e.col_scale && !(e.flags & BCOS_EPI_UNIT_NORM_W) &&
-                  (!e.row_scale || p.h2) &&
-                  !e.gate2 && !e.relu_gate && !(e.flags & (BCOS_EPI_NORM_ONLY | BCOS_EPI_FORCE_POW)) &&
-                  ((reinterpret_cast<uintptr_t>(e.bias) | reinterpret_cast<uintptr_t>(e.ch_scale) | reinterpret_cast<uintptr_t>(e.ch_shift)) & 15) == 0;
-        int ef = 0;
-        if (norm_l) {
-            ok = ok && e.b == 2.0f && e.relu >= 0 && e.relu <= 2 && !e.mul && !e.mul2 && !e.out2 && !e.out2_absmax &&
-                 !(e.flags & BCOS_EPI_MUL_FROM_ACT);
-            ef = (e.addend ? EF_ADDEND : 0) | (e.relu == 1 ? EF_RELU : 0) | (e.relu == 2 ? EF_GELU : 0) | (e.scale_out ? EF_SCALE_OUT : 0);
-        } else {
-            ok = ok && e.relu == 0 && !e.ch_scale && !e.ch_shift && !e.scale_out && (!e.mul2 || e.out2) &&
-                 (!e.out2 || e.mul) && (!e.out2_absmax || e.out2);
-            // out2 is either ungated or gated by the low bit of mul (BCOS_EPI_GATE2_FROM_MUL): both are what the kinds compute
-            ef = (e.addend ? EF_ADDEND : 0) | (e.mul ? EF_MUL : 0) | (e.out2 ? EF_OUT2 : 0) | (e.mul2 ? EF_MUL2 : 0) |
-                 ((e.flags & BCOS_EPI_MUL_FROM_ACT) ? EF_MULACT : 0) | (e.rowadd ? (EF_ROWADD | EF_ADDEND) : 0);
-            if (e.rowadd) ok = ok && e.rowadd_scale && e.addend_sub <= 1 && !(reinterpret_cast<uintptr_t>(e.rowadd) & 15) && g.out_cgroup == 0;
-            if (e.flags & BCOS_EPI_MUL_FROM_ACT)
-                ok = ok && ((reinterpret_cast<uintptr_t>(e.mul_csc) | reinterpret_cast<uintptr_t>(e.mul_csh)) & 15) == 0;
-        }
-        if (ok) {
-            const int* kinds = norm_l ? EPI_KINDS_FWD : EPI_KINDS_BWD;
-            for (int k = 0; k < N_EPI_KINDS; ++k)
-                if (kinds[k] == ef) { p.epi_kind = k + 1; p.out_bytes = (unsigned)obytes; break; }
-        }
-    }
-    if (epi->rowadd && (p.epi_kind == 0 || (epi->bcos_mode != BCOS_NONE)))
+    select_operands(c.ops, p);
+    uintptr_t bits = 0;
+    const void* ptrs[] = {e.addend, e.mul, e.mul2, e.gate2, e.relu_gate, e.out, e.out2, e.scale_out};
+    for (const void* q : ptrs) bits |= reinterpret_cast<uintptr_t>(q);
+    p.vec_ok = ((bits & 15) == 0 && g.out_pitch % 4 == 0) ? 1 : 0;
+    if (g.out_cgroup > 0 && !p.vec_ok)
+        return bcos_set_error(BCOS_E_INVAL, "bcos_tapconv: out_cgroup needs 16-byte addressable epilogue tensors");
+    select_epilogue_kind(p);
+    if (e.rowadd && (p.epi_kind == 0 || (e.bcos_mode != BCOS_NONE)))
         return bcos_set_error(BCOS_E_NOSUP, "bcos_tapconv: rowadd / rowadd_scale belong to a plain gradient launch that takes a specialised epilogue "
                                             "(16-byte addressable tensors < 2 GiB, Cout % 4 == 0, no mul / out2 / addend_sub): use bcos_patch_norm_bwd_add");
-    {   // per-image range of the emitted maxima (bcos_epilogue.out_imgmax / out_imgmin_c): folded into the specialised epilogues only, for
-        // launches whose tiles span at most 16 images (256 rows at >= 19 rows per image), plain output mapping, one group
-        const bool fuses = p.epi_kind > 0 && epi->out_absmax && g.out_cgroup == 0 && G == 1 && (int64_t)g.P * g.Q >= 19;
-        if (t_query_image_range) return fuses ? 1 : 0;
-        if (epi->out_imgmax || epi->out_imgmin_c) {
-            if (!epi->out_imgmax || !epi->out_imgmin_c || !fuses)
-                return bcos_set_error(BCOS_E_NOSUP, "bcos_tapconv: out_imgmax / out_imgmin_c come as a pair, with out_absmax, and only for launches "
-                                                    "bcos_tapconv_fuses_image_range() answers 1 for");
-        }
-    }
-    const bool norm = epi->bcos_mode != BCOS_NONE;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (g.Cout <= 8 && G == 1 && !epi->out_absmax && !epi->out2_absmax && epi->max_out <= 1 && epi->addend_sub <= 1 && !epi->row_scale && !epi->a_sumsq && !epi->rowadd) {
-        int ch_pass = 0;
-        const int handled = bcos_try_skinny(a, wt, p.g, p.e, p.M, s, t_query_route ? &ch_pass : nullptr);
-        if (handled > 0 && t_query_route) *t_query_route = bcos_tapconv_route{ROUTE_skinny, 0, 0, BCOS_LOOP_F32, 0, 0, 1, ch_pass};
-        if (handled != 0) return handled < 0 ? handled : BCOS_OK;
-    }
+    // per-image range of the emitted maxima (bcos_epilogue.out_imgmax / out_imgmin_c): folded into the specialised epilogues only, for
+    // launches whose tiles span at most 16 images (256 rows at >= 19 rows per image), plain output mapping, one group
+    *fuses = p.epi_kind > 0 && e.out_absmax && g.out_cgroup == 0 && g.groups <= 1 && (int64_t)g.P * g.Q >= 19;
+    return BCOS_OK;
+}
+
+// stage 3: which launcher a resolved launch takes -- a function of the descriptor (geometry, epilogue, p.h2 / p.a_imgmax) and the
+// option table; launches nothing
+#define BCOS_TC_GO(name) Route{ROUTE_##name, 0}
+Route choose_route(const KArgs& p) {
+    const bcos_tapconv_geom& g = p.g;
+    const bcos_epilogue& e = p.e;
+    const int G = g.groups > 1 ? g.groups : 1;
+    const int64_t M64 = p.M;
+    const bool narrow = g.Cout <= 8 && G == 1 && !e.out_absmax && !e.out2_absmax && e.max_out <= 1 && e.addend_sub <= 1 && !e.row_scale && !e.a_sumsq && !e.rowadd;
+    if (const int ch_pass = narrow ? bcos_skinny_ch_pass(g, e) : 0) return Route{ROUTE_skinny, ch_pass};
     if (p.h2) {
         // staging of the split-f16 loop: LDS-DMA (tile_body_d, default) or registers (tile_body_h2: BCOS_H2_LOOP=regs); same bits
         const bool dma = bcos_option(BCOS_OPT_H2_LOOP) == 0;
         {
             // multi-tap launches over an LDS-resident input patch (tile_body_p).  The choice depends on the layer's geometry alone,
             // never on the batch: the patch loop rounds differently from the per-tap loops (one operand scale per image), and an
-            // image's bits must not depend on how many images share its launch.  BCOS_OPT_PATCH = 0: development / test switch.
-            const bool patch_on = bcos_option(BCOS_OPT_PATCH) != 0;
-            if (!patch_on) { p.a_imgmax = p.a_imgmin = nullptr; p.a_imgmin_c = nullptr; }      // (per-row scales everywhere: the per-tap loops as they were)
+            // image's bits must not depend on how many images share its launch.  (BCOS_OPT_PATCH = 0: select_operands passed no p.a_imgmax on.)
             const int ntaps = g.TH * g.TW;
             const bool geom_ok = ((ntaps == 9 && g.TH == 3) || (ntaps == 16 && g.TH == 4)) && g.C % X3_BK == 0 && g.in_sh == 1 && g.in_sw == 1 &&
-                                 g.dstep_h == 1 && g.dstep_w == 1 && p.g.a_pitch >= g.C;
-            if (dma && geom_ok && p.a_imgmax && patch_on && !epi->row_scale && !epi->a_sumsq) {      // (the patch kernels compile those two out)
+                                 g.dstep_h == 1 && g.dstep_w == 1 && g.a_pitch >= g.C;
+            if (dma && geom_ok && p.a_imgmax && !e.row_scale && !e.a_sumsq) {      // (the patch kernels compile those two out)
                 if (ntaps == 16) {
                     if (g.Cout <= 32 && g.in_sh == 1) return BCOS_TC_GO(p2_256x32_t16);
                 } else {
@@ -4309,7 +4236,79 @@ extern "C" int bcos_tapconv_ops(const bcos_operands* ops, const bcos_tapconv_geo
     if (g.Cout > 32) return BCOS_TC_GO(cfg_128x64);
     return BCOS_TC_GO(cfg_128x32);
 }
+#undef BCOS_TC_GO
 
+// stage 4: the launcher of the route, or the narrow-output kernel
+int launch_route(const Route& r, const KArgs& p, hipStream_t s) {
+    if (r.id == ROUTE_skinny) return bcos_skinny_launch(p.a, p.wt, p.g, p.e, s);
+    return ROUTES[r.id].launch(&p, p.e.bcos_mode != BCOS_NONE ? 1 : 0, s);
+}
+
+// resolve -> the check of the out_imgmax / out_imgmin_c pair -> choose_route: everything of one launch but the launch
+int plan_launch(const Call& c, KArgs& p, Route* r) {
+    bool fuses = false;
+    const int rc = resolve(c, p, &fuses);
+    if (rc != BCOS_OK) return rc;
+    if ((c.e.out_imgmax || c.e.out_imgmin_c) && (!c.e.out_imgmax || !c.e.out_imgmin_c || !fuses))
+        return bcos_set_error(BCOS_E_NOSUP, "bcos_tapconv: out_imgmax / out_imgmin_c come as a pair, with out_absmax, and only for launches "
+                                            "bcos_tapconv_fuses_image_range() answers 1 for");
+    *r = choose_route(p);
+    return BCOS_OK;
+}
+}  // namespace
+
+extern "C" int bcos_tapconv_ops(const bcos_operands* ops, const bcos_tapconv_geom* geom, const bcos_epilogue* epi, void* stream) {
+    bcos_tapconv_geom g;
+    int rc = validate(ops, geom, epi, &g);
+    if (rc != BCOS_OK) return rc;
+    const int per = images_per_launch(*ops, g);
+    for (int n0 = 0; n0 < g.N; n0 += per) {
+        KArgs p; Route r;
+        rc = plan_launch(chunk_of(*ops, g, *epi, n0, per), p, &r);
+        if (rc == BCOS_OK) rc = launch_route(r, p, reinterpret_cast<hipStream_t>(stream));
+        if (rc != BCOS_OK) return rc;
+    }
+    return BCOS_OK;
+}
+
+// 1: a bcos_tapconv_ops call with these arguments folds the per-image range of its out_absmax into bcos_epilogue.out_imgmax / out_imgmin_c
+// itself; 0: it does not (general epilogue, depth-to-space or grouped launch, fewer than 19 rows per image, no out_absmax) and rejects
+// the two fields; < 0: the arguments are invalid anyway.  Nothing is launched: validate and resolve, as the launch runs them.
+extern "C" int bcos_tapconv_fuses_image_range(const bcos_operands* ops, const bcos_tapconv_geom* geom, const bcos_epilogue* epi) {
+    bcos_tapconv_geom g;
+    int rc = validate(ops, geom, epi, &g);
+    if (rc != BCOS_OK) return rc;
+    const int per = images_per_launch(*ops, g);
+    // (chunks differ in their image count alone, which decides the answer only through the 2 GiB limits: 1 if any chunk folds)
+    for (int n0 = 0; n0 < g.N; n0 += per) {
+        KArgs p; bool fuses = false;
+        rc = resolve(chunk_of(*ops, g, *epi, n0, per), p, &fuses);
+        if (rc != BCOS_OK) return rc;
+        if (fuses) return 1;
+    }
+    return 0;
+}
+
+extern "C" int bcos_tapconv_route_query(const bcos_operands* ops, const bcos_tapconv_geom* geom, const bcos_epilogue* epi, bcos_tapconv_route* out) {
+    if (!out) return bcos_set_error(BCOS_E_INVAL, "bcos_tapconv_route_query: NULL result");
+    *out = bcos_tapconv_route{-1, 0, 0, 0, 0, 0, 0, 0};
+    bcos_tapconv_geom g;
+    int rc = validate(ops, geom, epi, &g);
+    if (rc != BCOS_OK) return rc;
+    const int per = images_per_launch(*ops, g);
+    KArgs p; Route r;
+    rc = plan_launch(chunk_of(*ops, g, *epi, 0, per), p, &r);      // (the first chunk's route)
+    if (rc != BCOS_OK) return rc;
+    const RouteEntry& row = ROUTES[r.id];
+    const int chunks = (g.N + per - 1) / per;
+    if (r.id == ROUTE_skinny) *out = bcos_tapconv_route{r.id, 0, 0, BCOS_LOOP_F32, 0, 0, chunks, r.ch_pass};      // (its own plain epilogue)
+    else *out = bcos_tapconv_route{r.id, p.epi_kind, p.e.bcos_mode != BCOS_NONE ? 1 : 0, family_loop(row.fam, p), row.bm, row.bn, chunks, 0};
+    return BCOS_OK;
+}
+
+extern "C" const char* bcos_tapconv_route_name(int route) { return route >= 0 && route < ROUTE_COUNT ? ROUTES[route].name : nullptr; }
+extern "C" int bcos_tapconv_route_count(void) { return ROUTE_COUNT; }
+extern "C" int bcos_tapconv_epilogue_kinds(void) { return N_EPI_KINDS; }
 
 extern "C" int bcos_tapconv_group(const float* a, const float* const* wts, const bcos_tapconv_geom* geoms,
                                   const bcos_epilogue* epis, int count, void* stream) {

@@ -328,8 +328,8 @@ int bcos_tapconv(const float* a, const float* wt, const bcos_tapconv_geom* geom,
                  const bcos_epilogue* epi, void* stream);
 
 /* Which tile launcher, contraction loop and epilogue would bcos_tapconv_ops(ops, geom, epi, ...) run?  (ABI v11)  Launches nothing and needs no
- * device: the call walks bcos_tapconv_ops' own validation, operand and epilogue selection and its dispatch, and stops where the launch would
- * be issued -- the answer comes from the code that launches, under the option table and default contraction mode of the moment.  Returns 0 and
+ * device: the query and the launch share the same planning functions (argument validation, operand and epilogue selection, route choice) and
+ * only the launch goes on to a launcher -- the answer holds under the option table and default contraction mode of the moment.  Returns 0 and
  * fills *out, or the error code bcos_tapconv_ops returns for the same arguments (out == NULL: BCOS_E_INVAL).  Every compiled launcher has an
  * id in [0, bcos_tapconv_route_count()); the ids are not stable across versions, the names are.  bcos_tapconv_group's fused narrow-output
  * form (several tap sets in one launch) is outside the query: it reports what each entry would take on its own. */

@@ -91,7 +91,7 @@ GENERAL = Epi("g_b2p5", 0, bcos_mode=1, b=2.5, scale_out=True, norm_out=True, bi
 GENERAL_BWD = Epi("g_gate2", 0, mul=True, out2=True, mul2=True, gate2=True)            # the general epilogue of a plain / gradient launch
 ALL_KINDS = FWD_KINDS + BWD_KINDS + [GENERAL, GENERAL_BWD]
 
-# the reasons the dispatcher falls back to the general epilogue for (csrc/bcos_tapconv.hip, "specialised epilogue" block of bcos_tapconv_ops);
+# the reasons the dispatcher falls back to the general epilogue for (csrc/bcos_tapconv.hip: select_epilogue_kind, the "specialised epilogue" stage of the dispatch);
 # spread over the routes, one or two per route
 GENERAL_REASONS = [
     Epi("g_force_pow", 0, bcos_mode=1, flags=EPI_FORCE_POW, scale_out=True),
@@ -295,16 +295,16 @@ ROUTES = [
 # (forward kinds), 0 = plain.  The completeness test fails for a triple that is neither reached by a case nor listed here -- and for one that
 # is listed here and reached.
 UNREACHABLE = (
-    [("skinny", 1, k, "csrc/bcos_skinny.hip bcos_try_skinny: `if (e.bcos_mode != BCOS_NONE || ...) return 0` -- a B-cos launch never takes the narrow kernel")
+    [("skinny", 1, k, "csrc/bcos_skinny.hip skinny_decide: `if (e.bcos_mode != BCOS_NONE || ...) return false` -- a B-cos launch never takes the narrow kernel")
      for k in range(0, N_KINDS + 1)] +
-    [("skinny", 0, k, "csrc/bcos_tapconv.hip bcos_tapconv_ops: the narrow kernel has its own plain epilogue; the query reports epi_kind 0 for it")
+    [("skinny", 0, k, "csrc/bcos_tapconv.hip bcos_tapconv_route_query: the narrow kernel has its own plain epilogue; the query reports epi_kind 0 for it")
      for k in range(1, N_KINDS + 1)])
 
 # features the dispatcher keeps off a launcher family (asked per feature, not per kind): (route prefix, epilogue set, where the launch goes instead, source)
 FEATURE_DETOURS = [
-    ("p128a", F_ROW_SCALE, "d_128x64", "csrc/bcos_tapconv.hip: `if (dma && geom_ok && p.a_imgmax && patch_on && !epi->row_scale && !epi->a_sumsq)`"),
+    ("p128a", F_ROW_SCALE, "d_128x64", "csrc/bcos_tapconv.hip choose_route: `if (dma && geom_ok && p.a_imgmax && !e.row_scale && !e.a_sumsq)`"),
     ("p128a", B_ROW_SCALE, "d_128x64", "the same condition: the patch kernels compile row_scale out"),
-    ("d192_132", G_UNIT_NORM_W, "cfg_128x128", "csrc/bcos_tapconv.hip: `if (mode == 2 && G == 1 && h2_pays && !unit_w ...` -- BCOS_EPI_UNIT_NORM_W runs on the fp32 / bf16x3 loops"),
+    ("d192_132", G_UNIT_NORM_W, "cfg_128x128", "csrc/bcos_tapconv.hip select_operands: `if (mode == 2 && G == 1 && h2_pays && !unit_w ...` -- BCOS_EPI_UNIT_NORM_W runs on the fp32 / bf16x3 loops"),
 ]
 
 
@@ -324,7 +324,7 @@ def bcos_forward_errors(y, s, n, y64, s64, n64, norm_y, norm_s, tiny=1e-30):
 
 
 def loops_of(route_name):
-    """The contraction loops a launcher can run (csrc/bcos_tapconv.hip: launch_cfg picks among three, the others instantiate one)."""
+    """The contraction loops a launcher can run (csrc/bcos_tapconv.hip family_loop: launch_cfg picks among three, the others instantiate one)."""
     if route_name == "skinny":
         return ["f32"]
     fam = route_name.split("_")[0]
@@ -332,7 +332,7 @@ def loops_of(route_name):
 
 
 def rejected(r, e):
-    """Pairs bcos_tapconv_ops' argument validation rejects (include/bcos_hip.h): nothing is asked of them."""
+    """Pairs bcos_tapconv_ops' argument validation (csrc/bcos_tapconv.hip: validate) rejects (include/bcos_hip.h): nothing is asked of them."""
     if r.cgroup and (e.norm or e.max_out or e.absmax or e.norm_out or e.bias or e.ch_scale or e.ch_shift or (e.flags & EPI_MUL_FROM_ACT)
                      or e.rowadd or e.addend_sub > 1 or e.row_scale or e.misalign):
         return True                                          # out_cgroup launches are plain gradient launches

@@ -1,10 +1,11 @@
 """The dispatcher of bcos_tapconv_ops against the case table (tests/tapconv_cases.py), without a device: the route query
-(include/bcos_hip.h: bcos_tapconv_route_query) walks the launch path's own validation and selection and launches nothing.
+(include/bcos_hip.h: bcos_tapconv_route_query) runs the launch path's own planning functions and launches nothing.
 
   * every case takes the launcher, loop and epilogue kind the table expects, under the options the case sets;
   * the table is complete: every (route, loop, direction, epilogue kind) the library can report is reached by a case or listed as
     unreachable with the source line that makes it so -- a launcher nobody tests is a failure, and so is a stale exemption;
-  * the query is pure, and rejects what the launch rejects with the launch's error code.
+  * the query is pure, and rejects what the launch rejects with the launch's error code;
+  * the image-range question (bcos_tapconv_fuses_image_range) is answered by the rule the header documents, for every case.
 """
 import ctypes as C
 
@@ -111,6 +112,28 @@ def test_features_the_dispatcher_keeps_off_a_launcher(blib, detour):
     r = next(x for x in tc.ROUTES if x.name == name)
     q, _ = _query(blib, tc.Case(r, epi))
     assert q["route"] != r.route and q["route"] == instead, (q, why)
+
+
+def test_image_range_answer_follows_the_documented_rule(blib):
+    """include/bcos_hip.h: the launch folds the per-image range of its out_absmax itself iff it takes a specialised epilogue, emits
+    out_absmax, maps its output plainly (no depth to space), has one group and at least 19 rows per image"""
+    lib = blib.load()
+    wrong = []
+    for case in tc.CASES:
+        r = case.r
+        b = tc.Built(case, "cpu", blib)
+        args = (C.byref(b.ops), C.byref(b.geom), C.byref(b.epi))
+        expect = int(case.kind > 0 and case.absmax and not r.cgroup and max(r.groups, 1) == 1 and r.P * r.Q >= 19)
+        with tc.with_options(blib, b.options()):
+            got = lib.bcos_tapconv_fuses_image_range(*args)
+        if got != expect:
+            wrong.append((case.id, got, expect))
+        if r.name in ("cfg64_chunks", "d64_chunks"):        # the batch-chunk path answers what the unchunked call answers
+            assert "split_limit" in b.options()
+            with tc.with_options(blib, {k: v for k, v in b.options().items() if k != "split_limit"}):
+                assert lib.bcos_tapconv_fuses_image_range(*args) == got, case.id
+    assert not wrong, wrong
+    assert {r.name for r in tc.ROUTES if dict(r.opts).get("split_limit")} == {"cfg64_chunks", "d64_chunks"}
 
 
 def test_query_is_pure_and_leaves_the_options_alone(blib):
