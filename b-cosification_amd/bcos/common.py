@@ -92,7 +92,7 @@ class BcosUtilMixin:
 
     # -- batched explanation (MI355X addition) -----------------------------------------------------------
     def explain_batch(self, images: Tensor, targets: Optional[Tensor] = None, render: bool = False,
-                      smooth: int = 15, alpha_percentile: float = 99.5) -> "Dict[str, Tensor]":
+                      smooth: int = 15, alpha_percentile: float = 99.5, functional=None) -> "Dict[str, Tensor]":
         """Forward + explanation for a whole batch.
 
         Returns logits [N,K], prediction [N], explained_class_idx [N], dynamic_linear_weights [N,C,H,W]
@@ -100,8 +100,10 @@ class BcosUtilMixin:
         Uses the fused engine when one is attached (`bcos_hip.engine.attach`), else autograd over the modules.
         `render=True` adds "explanation" [N,H,W,4]: the RGBA images of `gradient_to_image` for the whole batch, rendered
         on the device (bcos_render_explanations).
+        `functional` (a bcos_hip.functional.LogitFunctional, instead of `targets`): explain a linear functional sum_k c_k y_k of the
+        logits -- a contrast y_a - y_b, the mean-corrected y_t - mean_k y_k --; `functional_value` [N] replaces `explained_class_idx`.
         """
-        out = self._explain_batch(images, targets)
+        out = self._explain_batch(images, targets, functional)
         if render:
             from bcos_hip import ops
             out["explanation"] = ops.render_explanations(images.detach().contiguous(),
@@ -109,14 +111,22 @@ class BcosUtilMixin:
                                                          alpha_percentile=alpha_percentile)
         return out
 
-    def _explain_batch(self, images: Tensor, targets: Optional[Tensor] = None) -> "Dict[str, Tensor]":
+    def _explain_batch(self, images: Tensor, targets: Optional[Tensor] = None, functional=None) -> "Dict[str, Tensor]":
         engine = getattr(self, "_bcos_engine", None)
         if engine is not None and getattr(engine, "supports_explain", True) and not self.training:
-            return engine.explain(images, targets)
+            return engine.explain(images, targets) if functional is None else engine.explain(images, targets, functional=functional)
         x = images.detach().clone().requires_grad_(True)
         with torch.enable_grad(), self.explanation_mode():
             logits = self(x)  # noqa
             pred = logits.max(1)
+            if functional is not None:
+                if targets is not None:
+                    raise ValueError("explain_batch: `functional` replaces `targets`: pass one of them")
+                f = functional.checked(x.shape[0], logits.shape[1]).to(logits.device)
+                (grad,) = torch.autograd.grad(f.value(logits).sum(), x)
+                from bcos_hip import ops
+                return dict(logits=logits.detach(), prediction=pred.indices, functional_value=f.value(logits.detach()),
+                            dynamic_linear_weights=grad, contribution_map=ops.contrib_map(x.detach().contiguous(), grad.contiguous()))
             idx = pred.indices if targets is None else targets.to(logits.device)
             (grad,) = torch.autograd.grad(logits.gather(1, idx.view(-1, 1)).sum(), x)
         from bcos_hip import ops

@@ -25,6 +25,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
+from .functional import LogitFunctional, as_functional
 from .lib import (BCOS_CONV_EPS, BCOS_EPI_FORCE_POW, BCOS_EPI_GATE2_FROM_MUL, BCOS_EPI_MUL_FROM_ACT, BCOS_EPI_SCALE_GATE_LSB,
                   BCOS_NONE, BcosHipError)
 
@@ -764,7 +765,7 @@ class ResNetEngine:
 
     @torch.no_grad()
     def explain(self, x: torch.Tensor, targets: Optional[torch.Tensor] = None, want_weights: bool = True,
-                gates=None, cotangent=None) -> Dict[str, torch.Tensor]:
+                gates=None, cotangent=None, functional: Optional[LogitFunctional] = None) -> Dict[str, torch.Tensor]:
         """Forward in explanation mode + input-gradient pass of the explained logit of every image
         (batched bcos/common.py:163-181).  `targets` [N] int64 selects the logits (default: arg-max).
         `gates`: optional list of NHWC 0/1 tensors, one per ReLU in execution order, that REPLACE the v > 0
@@ -772,13 +773,33 @@ class ResNetEngine:
         `cotangent` (attention-pool heads): a callable that receives the head output -- the embeddings [N, D], or [(HW), N, D']
         for an `attn_unpool` head -- and returns d(scalar to explain) / d(head output) of the same shape; the input-gradient
         pass then starts from it instead of from a one-hot coordinate (the zero-shot text logit of
-        interpretability/analyses/text_localisation.py:68-126: bcos_hip.clip_head.zeroshot_attribution)."""
+        interpretability/analyses/text_localisation.py:68-126: bcos_hip.clip_head.zeroshot_attribution).
+        `functional` (bcos_hip.functional.LogitFunctional, instead of `targets`): explain a linear functional sum_k c_k y_k of the logits --
+        a contrast y_a - y_b, the mean-corrected y_t - mean_k y_k -- at the cost of one ordinary pass (the network is linear in the head
+        cotangent); the result carries `functional_value` [N] (sum_k c_k logit_k) in place of `explained_class_idx`."""
+        functional = self._checked_functional(x, functional, targets, cotangent)
         if targets is not None and self.head_kind == "gap_fc":
             targets = ops.check_targets(targets, self.head.cout)       # IndexError like the reference's out[0, idx]; negative indices wrap
         S = self.n_streams(x, cotangent=cotangent)
         if S > 1:
-            return self._explain_subbatches(x, targets, want_weights, S, gates)
-        return self._explain_one(x, targets, want_weights, gates, cotangent, self._absmax_arena)
+            return self._explain_subbatches(x, targets, want_weights, S, gates, functional)
+        return self._explain_one(x, targets, want_weights, gates, cotangent, self._absmax_arena, functional=functional)
+
+    def n_logits(self) -> int:
+        """width of the head output a target index / a functional's cotangent refers to (attention-pool heads: the embedding)"""
+        return self.head.cout if self.head_kind == "gap_fc" else self.ap_w["c"].shape[0]
+
+    def _checked_functional(self, x, functional, targets=None, cotangent=None):
+        """a `functional` argument validated on the host before any launch and moved to x's device (None stays None)"""
+        functional = as_functional(functional)
+        if functional is None:
+            return None
+        if targets is not None or cotangent is not None:
+            raise ValueError("engine: `functional` replaces `targets` / `cotangent`: pass one of them")
+        if self.head_kind == "attn_unpool":
+            raise BcosHipError("engine: an attn_unpool head has no class logits of its own: pass `cotangent` "
+                               "(bcos_hip.clip_head.zeroshot_attribution builds it from the text embeddings)")
+        return functional.checked(x.shape[0], self.n_logits()).to(x.device)
 
     def n_streams(self, x, cotangent=None) -> int:
         """On how many sub-batch streams does explain(x, ...) run?  `subbatch_streams` (default 2) for a batch of at least that many
@@ -809,7 +830,7 @@ class ResNetEngine:
             return 1
         return S
 
-    def _explain_subbatches(self, x, targets, want_weights, S, gates=None):
+    def _explain_subbatches(self, x, targets, want_weights, S, gates=None, functional=None):
         """explain() of S contiguous sub-batches on S side streams, written into ONE set of output tensors (see
         _SUBBATCH_STREAMS).  The side streams start behind the caller's stream and the caller's stream waits for them."""
         streams, arenas = self._side_for(x, S)
@@ -827,12 +848,13 @@ class ResNetEngine:
             streams[i].wait_stream(cur)
             sub_gates = None if gates is None else [gt[lo:hi] for gt in gates]       # (replayed ReLU decisions: [N, ...] like the activations)
             gens.append(self._explain_one_gen(x[lo:hi], None if tg is None else tg[lo:hi], want_weights, sub_gates, None,
-                                              outs=(wts[lo:hi] if want_weights else None, contrib[lo:hi])))
+                                              outs=(wts[lo:hi] if want_weights else None, contrib[lo:hi]),
+                                              functional=None if functional is None else functional[lo:hi].to(x.device)))
         parts = _interleave(gens, streams, arenas, x.device)
         for st in streams[:S]:
             cur.wait_stream(st)
         res = {}
-        for k in ("logits", "prediction", "explained_class_idx"):
+        for k in ("logits", "prediction", "explained_class_idx" if functional is None else "functional_value"):
             ts = [p[k] for p in parts]
             for t in ts:
                 t.record_stream(cur)             # allocated in a side stream's pool, read by the cat on the caller's stream
@@ -840,11 +862,11 @@ class ResNetEngine:
         res.update(dynamic_linear_weights=wts, contribution_map=contrib)
         return res
 
-    def _explain_one(self, x, targets, want_weights, gates, cotangent, arena, outs=None):
+    def _explain_one(self, x, targets, want_weights, gates, cotangent, arena, outs=None, functional=None):
         with ops.absmax_arena(arena, x.device):
-            return _drive(self._explain_one_gen(x, targets, want_weights, gates, cotangent, outs))
+            return _drive(self._explain_one_gen(x, targets, want_weights, gates, cotangent, outs, functional))
 
-    def _explain_one_gen(self, x, targets, want_weights, gates, cotangent, outs=None):
+    def _explain_one_gen(self, x, targets, want_weights, gates, cotangent, outs=None, functional=None):
         """forward + input-gradient pass of one (sub-)batch as a generator (yields behind every block of either pass); the caller owns
         the stream and the maxima arena the launches are issued under"""
         logits, st = yield from self._run_forward_gen(x, keep=True, gates=gates)
@@ -860,6 +882,10 @@ class ResNetEngine:
             raise BcosHipError("engine: an attn_unpool head has no class logits of its own: pass `cotangent` "
                                "(bcos_hip.clip_head.zeroshot_attribution builds it from the text embeddings)")
         pred, _ = ops.argmax_rows(logits)
+        if functional is not None:
+            wts, contrib = yield from self._backward_gen(x, st, None, want_weights, consume=True, outs=outs, functional=functional)
+            return dict(logits=logits, prediction=pred, functional_value=functional.value(logits), dynamic_linear_weights=wts,
+                        contribution_map=contrib)
         if targets is not None and self.head_kind != "gap_fc":
             targets = ops.check_targets(targets, logits.shape[1])      # (attention-pool head: the embedding width; gap_fc heads were checked in explain())
         cls = pred if targets is None else targets.to(device=logits.device, dtype=torch.int64).contiguous()
@@ -895,12 +921,39 @@ class ResNetEngine:
             out["dynamic_linear_weights"] = wall
         return out
 
-    def _backward(self, x, st, cls, want_weights: bool, consume: bool, g_head=None, outs=None):
-        return _drive(self._backward_gen(x, st, cls, want_weights, consume, g_head, outs))
+    @torch.no_grad()
+    def explain_functionals(self, x: torch.Tensor, functionals, want_weights: bool = False) -> Dict[str, torch.Tensor]:
+        """ONE forward in explanation mode, then one input-gradient pass per LogitFunctional of `functionals` (each over the whole
+        batch) -- explain_targets for functionals: the kept forward does not depend on what is explained.
+        Returns logits [N, K], functional_values [N, T], contribution_maps [N, T, H, W] and, if requested, dynamic_linear_weights
+        [N, T, 6, H, W]."""
+        fs = [self._checked_functional(x, f) for f in functionals]
+        if not fs or any(f is None for f in fs):
+            raise ValueError("explain_functionals: a non-empty list of LogitFunctional objects")
+        T = len(fs)
+        with ops.absmax_arena(self._absmax_arena, x.device):
+            logits, st = self._run_forward(x, keep=True)
+            maps = torch.empty((x.shape[0], T, st["H"], st["W"]), device=x.device, dtype=torch.float32)
+            wall = torch.empty((x.shape[0], T, 6, st["H"], st["W"]), device=x.device, dtype=torch.float32) if want_weights else None
+            for k, f in enumerate(fs):
+                wts, contrib = self._backward(x, st, None, want_weights, consume=(k == T - 1), functional=f)
+                maps[:, k] = contrib
+                if want_weights:
+                    wall[:, k] = wts
+        out = dict(logits=logits, functional_values=torch.stack([f.value(logits) for f in fs], 1), contribution_maps=maps)
+        if want_weights:
+            out["dynamic_linear_weights"] = wall
+        return out
 
-    def _backward_gen(self, x, st, cls, want_weights: bool, consume: bool, g_head=None, outs=None):
+    def _backward(self, x, st, cls, want_weights: bool, consume: bool, g_head=None, outs=None, functional=None):
+        return _drive(self._backward_gen(x, st, cls, want_weights, consume, g_head, outs, functional))
+
+    def _backward_gen(self, x, st, cls, want_weights: bool, consume: bool, g_head=None, outs=None, functional=None):
         """Input-gradient pass of logit[cls[n]] for every image n over the state `st` of a kept forward; `consume` frees
-        each saved multiplier as soon as it has been used (last / only pass over this state)."""
+        each saved multiplier as soon as it has been used (last / only pass over this state).  `functional` (instead of `cls`): the
+        pass of sum_k c_k logit[k] -- only its first launch differs."""
+        if functional is not None and self.head_kind == "attnpool":       # a functional over the embedding coordinates: the dense g_emb
+            g_head = functional.as_dense(self.n_logits())
         # A "consumer" owns the g_lin tensors of the layers that read some activation X and can therefore
         # finish d logit / d X; its epilogue applies the multipliers of the block that PRODUCED X.
         if self.head_kind == "attnpool":
@@ -910,8 +963,20 @@ class ResNetEngine:
         else:
             # d logit[cls] / d (head lin): one-hot * 1/(T*HW) * head scale
             hc = self.head
-            if (_HEAD_RANK1 and hc.k == (1, 1) and hc.stride == (1, 1) and hc.padding == (0, 0) and getattr(hc, "groups", 1) == 1
-                    and int(getattr(hc.module, "max_out", 1)) == 1 and hc.w_fwd.shape[-1] % 4 == 0 and hc.w_fwd.shape[-1] == hc.cin):
+            rank1_ok = (_HEAD_RANK1 and hc.k == (1, 1) and hc.stride == (1, 1) and hc.padding == (0, 0) and getattr(hc, "groups", 1) == 1
+                        and int(getattr(hc.module, "max_out", 1)) == 1 and hc.w_fwd.shape[-1] % 4 == 0 and hc.w_fwd.shape[-1] == hc.cin)
+            if functional is not None and functional.is_sparse and rank1_ok:
+                # a few classes per image: the rank-one launch with a short sum of weight rows (ops.head_rankm_grad)
+                consumer = _HeadRankMConsumer(functional.classes, st["tf"], hc.w_fwd.view(hc.w_fwd.shape[0], -1), self.logit_temperature,
+                                              coef=functional.coeffs)
+            elif functional is not None:
+                # any functional: its cotangent times the head's scale (ops.head_cotangent_grad, the one-hot tensor's general form, with
+                # its row maxima), then the head's own input-gradient contraction
+                if hc.cout % 4 != 0:
+                    raise BcosHipError(f"engine: the dense head gradient of a functional needs a head width that is a multiple of 4 (got {hc.cout})")
+                g_head = ops.head_cotangent_grad(functional.as_dense(hc.cout), st["tf"], self.logit_temperature)
+                consumer = _Consumer(self.head, g_head, None, None, 0)
+            elif rank1_ok:
                 # ... carried through the head's 1 x 1 convolution at once: the gradient is rank one per image (one class column of
                 # the head's scale x one weight row), a streaming launch instead of the [N, 7, 7, 1000] one-hot tensor, a pass for its
                 # row maxima and a K = 1000 contraction over 999 zero columns
@@ -1044,16 +1109,19 @@ class _HeadRank1Consumer:
     def __init__(self, cls, tf, w, temperature):
         self.cls, self.tf, self.w, self.temperature = cls, tf, w, temperature
 
+    def _grad(self, tf, **kw):
+        return ops.head_rank1_grad(self.cls, tf, self.w, self.temperature, **kw)
+
     def run(self, H, W, t_main, td, gated, gate_t=None, track=None, track2=None):
         N, K, D = self.tf.shape[0], self.tf.shape[-1], self.w.shape[1]
         tf = self.tf.view(N, H * W, K)
         if t_main is None:
-            out, _ = ops.head_rank1_grad(self.cls, tf, self.w, self.temperature, want_absmax=bool(track))
+            out, _ = self._grad(tf, want_absmax=bool(track))
             out = self._nhwc(out, N, H, W, D)
             return out, out
         flat = lambda t: None if t is None else (t if t.is_contiguous() else t.contiguous()).view(N * H * W, D)      # noqa: E731
-        out, out2 = ops.head_rank1_grad(self.cls, tf, self.w, self.temperature, mul=flat(t_main), want_out2=True, mul2=flat(td), gate2=flat(gate_t),
-                                        gate2_from_mul=bool(gated and gate_t is None), want_absmax=bool(track), want_absmax2=bool(track2))
+        out, out2 = self._grad(tf, mul=flat(t_main), want_out2=True, mul2=flat(td), gate2=flat(gate_t),
+                               gate2_from_mul=bool(gated and gate_t is None), want_absmax=bool(track), want_absmax2=bool(track2))
         return self._nhwc(out, N, H, W, D), self._nhwc(out2, N, H, W, D)
 
     @staticmethod
@@ -1063,6 +1131,17 @@ class _HeadRank1Consumer:
         if am is not None:
             ops._attach_absmax(v, am)
         return v
+
+
+class _HeadRankMConsumer(_HeadRank1Consumer):
+    """... for a sparse linear functional of the logits: a few classes per image, each with a coefficient (ops.head_rankm_grad)."""
+
+    def __init__(self, cls, tf, w, temperature, coef):
+        super().__init__(cls, tf, w, temperature)
+        self.coef = coef
+
+    def _grad(self, tf, **kw):
+        return ops.head_rankm_grad(self.cls, self.coef, tf, self.w, self.temperature, **kw)
 
 
 class _RawConsumer:

@@ -1287,6 +1287,79 @@ def head_rank1_grad(cls, scale, w, temperature=None, row_scale=None, mul=None, w
     return out, out2
 
 
+HEAD_RANKM_MAX_TERMS = 8        # include/bcos_hip.h: bcos_head_rankm_grad takes 1 <= J <= 8 classes per image
+
+
+def check_functional_classes(classes, n_logits: int, what: str = "functional classes"):
+    """The class indices [N, J] of a sparse logit functional, validated ONCE on the host with the semantics of check_targets (an index in
+    [-K, -1] counts from the end, anything outside [-K, K) is the IndexError of the reference's `out[0, idx]`); a shape other than [N, J]
+    with J >= 1 is a ValueError.  Lists and host tensors cost no device synchronisation."""
+    t = check_targets(classes, n_logits, what)
+    if t is None or t.dim() != 2 or t.shape[1] < 1:
+        raise ValueError(f"{what}: expected class indices of shape [N, J] with J >= 1, got {None if t is None else tuple(t.shape)}")
+    return t
+
+
+def head_rankm_grad(cls, coef, scale, w, temperature=None, row_scale=None, mul=None, want_out2=False, want_absmax=False, mul2=None,
+                    gate2=None, gate2_from_mul=False, want_absmax2=False):
+    """head_rank1_grad for a sparse linear functional of the logits (include/bcos_hip.h: bcos_head_rankm_grad): cls [N, J] int64 and
+    coef [N, J] fp32, 1 <= J <= 8 -> (out [N R, D] = v * mul, out2 or None) with v = sum_j coef_j * (inv_t / R * scale[n, r, cls_j] *
+    row_scale * w[cls_j]), one fp32 chain in ascending j; the outputs and their maxima as head_rank1_grad."""
+    lib = _l.load()
+    N, R, K = scale.shape
+    D = w.shape[1]
+    if cls.dim() != 2 or cls.shape[0] != N or tuple(coef.shape) != tuple(cls.shape):
+        raise ValueError(f"head_rankm_grad: cls {tuple(cls.shape)} / coef {tuple(coef.shape)} do not match [N = {N}, J]")
+    J = cls.shape[1]
+    if not 1 <= J <= HEAD_RANKM_MAX_TERMS:
+        raise ValueError(f"head_rankm_grad: {J} classes per image (1 .. {HEAD_RANKM_MAX_TERMS}; head_cotangent_grad takes any functional)")
+    if cls.dtype != torch.int64 or not cls.is_cuda or not cls.is_contiguous():
+        raise BcosHipError("head_rankm_grad: cls must be a contiguous int64 HIP tensor")
+    for name, t in (("mul", mul), ("mul2", mul2), ("gate2", gate2)):
+        if t is not None and (t.numel() != N * R * D or not t.is_contiguous()):
+            raise BcosHipError(f"head_rankm_grad: {name} {tuple(t.shape)} does not match {(N * R, D)}")
+    if tuple(w.shape) != (K, D):
+        raise BcosHipError(f"head_rankm_grad: w {tuple(w.shape)} does not match scale {tuple(scale.shape)}")
+    want_out2 = bool(want_out2 or mul2 is not None or gate2 is not None or gate2_from_mul or want_absmax2)
+    out = torch.empty((N * R, D), device=scale.device, dtype=torch.float32)
+    out2 = torch.empty_like(out) if want_out2 else None
+    f16 = _l.get_contraction_mode() == "f16x2"
+    am = torch.empty((N * R,), device=scale.device, dtype=torch.int32) if (want_absmax and f16) else None
+    am2 = torch.empty((N * R,), device=scale.device, dtype=torch.int32) if (want_absmax2 and f16 and want_out2) else None
+    inv_t = 1.0 if temperature is None else 1.0 / float(temperature)
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None      # noqa: E731
+    _l.check(lib.bcos_head_rankm_grad(ptr(cls), _dev(coef, "coef"), J, _dev(scale, "scale"), _dev(w, "w"), _dev(row_scale, "row_scale"),
+                                      _dev(mul, "mul"), _dev(mul2, "mul2"), _dev(gate2, "gate2"), int(bool(gate2_from_mul)), _dev(out, "out"),
+                                      _dev(out2, "out2"), ptr(am), ptr(am2), N, R, K, D, inv_t, _stream()), "bcos_head_rankm_grad")
+    if am is not None:
+        _attach_absmax(out, am)
+    if am2 is not None:
+        _attach_absmax(out2, am2)
+    return out, out2
+
+
+def head_cotangent_grad(cot, scale, temperature=None, want_absmax=True):
+    """The gradient of a dense linear functional of the logits w.r.t. the head's `lin` (include/bcos_hip.h: bcos_head_cotangent_grad):
+    cot [N, K], scale [N, ..., K] -> glin [N, ..., Kp] = cot[n, k] * scale * inv_t / R, R the rows per image, Kp = K rounded up to 4 (zero
+    pad columns), with its row maxima attached while the f16x2 contraction is selected -- what the head's input-gradient contraction
+    reads.  head_onehot_grad is the case of a one-hot cot."""
+    lib = _l.load()
+    N, K = scale.shape[0], scale.shape[-1]
+    if cot.dim() != 2 or tuple(cot.shape) != (N, K):
+        raise ValueError(f"head_cotangent_grad: cot {tuple(cot.shape)} does not match scale {tuple(scale.shape)} ([N, K] = {(N, K)})")
+    R = scale.numel() // (N * K)
+    Kp = (K + 3) // 4 * 4
+    out = torch.empty(tuple(scale.shape[:-1]) + (Kp,), device=scale.device, dtype=torch.float32)
+    am = torch.empty((N * R,), device=scale.device, dtype=torch.int32) if (want_absmax and _l.get_contraction_mode() == "f16x2") else None
+    inv_t = 1.0 if temperature is None else 1.0 / float(temperature)
+    _l.check(lib.bcos_head_cotangent_grad(_dev(cot, "cot"), _dev(scale, "scale"), _dev(out, "glin"),
+                                          C.c_void_p(am.data_ptr()) if am is not None else None, N, R, K, inv_t, _stream()),
+             "bcos_head_cotangent_grad")
+    if am is not None:
+        _attach_absmax(out, am)
+    return out
+
+
 def argmax_rows(x2d):
     lib = _l.load()
     N, Cc = x2d.shape

@@ -20,6 +20,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
+from .functional import LogitFunctional, as_functional
 from .lib import BCOS_EPI_FORCE_POW, BCOS_LINEAR_EPS, BcosHipError
 
 
@@ -428,9 +429,13 @@ class ViTEngine:
         return outs[0] if len(outs) == 1 else torch.cat(outs)
 
     @torch.no_grad()
-    def explain(self, x, targets: Optional[torch.Tensor] = None, want_weights: bool = True) -> Dict[str, torch.Tensor]:
+    def explain(self, x, targets: Optional[torch.Tensor] = None, want_weights: bool = True,
+                functional: Optional[LogitFunctional] = None) -> Dict[str, torch.Tensor]:
+        """`functional` (bcos_hip.functional.LogitFunctional, instead of `targets`): the pass of a linear functional sum_k c_k y_k of the
+        logits (engine.ResNetEngine.explain); the result carries `functional_value` [N] in place of `explained_class_idx`."""
         x = x.detach()
         x = x if x.is_contiguous() else x.contiguous()
+        functional = self._checked_functional(x, functional, targets)
         targets = ops.check_targets(targets, self.head.cout)      # IndexError like the reference's out[0, idx]; negative indices wrap
         tg = None if targets is None else targets.to(device=x.device, dtype=torch.int64).contiguous()
 
@@ -442,37 +447,103 @@ class ViTEngine:
 
         def one(lo, hi):
             return self._explain_gen(x[lo:hi], None if tg is None else tg[lo:hi], want_weights,
-                                     outs=(wts[lo:hi] if want_weights else None, contrib[lo:hi]))
+                                     outs=(wts[lo:hi] if want_weights else None, contrib[lo:hi]),
+                                     functional=None if functional is None else functional[lo:hi].to(x.device))
         outs = self._sub_batches(x, one)
-        res = {k: (outs[0][k] if len(outs) == 1 else torch.cat([o[k] for o in outs])) for k in ("logits", "prediction", "explained_class_idx")}
+        res = {k: (outs[0][k] if len(outs) == 1 else torch.cat([o[k] for o in outs]))
+               for k in ("logits", "prediction", "explained_class_idx" if functional is None else "functional_value")}
         res.update(dynamic_linear_weights=wts, contribution_map=contrib)
         return res
+
+    def n_logits(self) -> int:
+        return self.head.cout
+
+    def _checked_functional(self, x, functional, targets=None):
+        """a `functional` argument validated on the host before any launch and moved to x's device (None stays None)"""
+        functional = as_functional(functional)
+        if functional is None:
+            return None
+        if targets is not None:
+            raise ValueError("vit engine: `functional` replaces `targets`: pass one of them")
+        return functional.checked(x.shape[0], self.head.cout).to(x.device)
+
+    @torch.no_grad()
+    def explain_functionals(self, x, functionals, want_weights: bool = False) -> Dict[str, torch.Tensor]:
+        """ONE forward in explanation mode, then one input-gradient pass per LogitFunctional of `functionals`
+        (engine.ResNetEngine.explain_functionals) -> logits [N, K], functional_values [N, T], contribution_maps [N, T, H, W] and, if
+        requested, dynamic_linear_weights [N, T, 6, H, W]."""
+        from .engine import _drive
+        x = x.detach()
+        x = x if x.is_contiguous() else x.contiguous()
+        fs = [self._checked_functional(x, f) for f in functionals]
+        if not fs or any(f is None for f in fs):
+            raise ValueError("explain_functionals: a non-empty list of LogitFunctional objects")
+        N, _, H, W = x.shape
+        nf = len(fs)
+        maps = torch.empty((N, nf, H, W), device=x.device, dtype=torch.float32)
+        wall = torch.empty((N, nf, 6, H, W), device=x.device, dtype=torch.float32) if want_weights else None
+        with _absmax_policy(), ops.absmax_arena(self._absmax_arena, x.device):
+            logits, st = self._run_forward(x, keep=True)
+            for k, f in enumerate(fs):
+                wts, contrib = _drive(self._backward_gen(x, st, None, want_weights, functional=f, consume=(k == nf - 1)))
+                maps[:, k] = contrib
+                if want_weights:
+                    wall[:, k] = wts
+        out = dict(logits=logits, functional_values=torch.stack([f.value(logits) for f in fs], 1), contribution_maps=maps)
+        if want_weights:
+            out["dynamic_linear_weights"] = wall
+        return out
 
     def _explain(self, x, targets, want_weights):
         from .engine import _drive
         return _drive(self._explain_gen(x, targets, want_weights))
 
-    def _explain_gen(self, x, targets, want_weights, outs=None):
+    def _explain_gen(self, x, targets, want_weights, outs=None, functional=None):
         logits, st = yield from self._run_forward_gen(x, keep=True)
-        N, T = st["N"], st["T"]
         pred, _ = ops.argmax_rows(logits)
+        if functional is not None:
+            wts, contrib = yield from self._backward_gen(x, st, None, want_weights, outs, functional)
+            return dict(logits=logits, prediction=pred, functional_value=functional.value(logits), dynamic_linear_weights=wts,
+                        contribution_map=contrib)
         cls = pred if targets is None else targets.to(device=logits.device, dtype=torch.int64).contiguous()
+        wts, contrib = yield from self._backward_gen(x, st, cls, want_weights, outs)
+        return dict(logits=logits, prediction=pred, explained_class_idx=cls, dynamic_linear_weights=wts,
+                    contribution_map=contrib)
+
+    def _head_grad(self, cls, functional, scale):
+        """gradient of the explained output w.r.t. the head's `lin` (scale [N, R, 1, K] -> [N, R, 1, K]): the one-hot tensor of a class
+        per image, or a functional's cotangent times the scale (ops.head_cotangent_grad, with its row maxima)"""
+        if functional is None:
+            return ops.head_onehot_grad(cls, scale, self.logit_temperature)
+        K = self.head.cout
+        if K % 4 != 0:
+            raise BcosHipError(f"vit engine: the dense head gradient of a functional needs a head width that is a multiple of 4 (got {K})")
+        return ops.head_cotangent_grad(functional.as_dense(K), scale, self.logit_temperature, want_absmax=_F16X2)
+
+    def _backward_gen(self, x, st, cls, want_weights, outs=None, functional=None, consume=True):
+        """input-gradient pass of logit[cls[n]] -- or of `functional` -- over the state of a kept forward; `consume` frees each block's
+        saved tensors once used (the last / only pass over this state)"""
+        N, T = st["N"], st["T"]
         nb = len(self.blocks)
         t_last = st["blocks"][-1]["t2"] if nb else st["t_embed"]
-        if self.gap_reorder and _LN_FUSED and _HEAD_RANK1 and self.dim % 4 == 0:
+        rank1 = self.gap_reorder and _LN_FUSED and _HEAD_RANK1 and self.dim % 4 == 0
+        if rank1 and functional is not None and functional.is_sparse:
+            g_lin, g_x = ops.head_rankm_grad(functional.classes, functional.coeffs, st["t_head"].view(N, T, -1), self.head.w_ln,
+                                             self.logit_temperature, row_scale=st["rstd_h"], mul=t_last, want_out2=True, want_absmax=_F16X2)
+        elif rank1 and functional is None:
             # d mean-logit[cls] / d (head input) is rank one per image: one class column of the stored scale times one row of the folded
             # weights -- a streaming launch instead of the [N T, K] one-hot tensor and a K-long contraction over it
             g_lin, g_x = ops.head_rank1_grad(cls, st["t_head"].view(N, T, -1), self.head.w_ln, self.logit_temperature, row_scale=st["rstd_h"],
                                              mul=t_last, want_out2=True, want_absmax=_F16X2)
         elif self.gap_reorder:
-            g_head = ops.head_onehot_grad(cls, st["t_head"].view(N, T, 1, -1), self.logit_temperature)     # [N,T,1,K]
+            g_head = self._head_grad(cls, functional, st["t_head"].view(N, T, 1, -1))     # [N,T,1,K]
             if _LN_FUSED:
-                g_lin, g_x = self.head.dgrad_ln(_mx(g_head.view(N * T, -1)), st["rstd_h"], mul=t_last)
+                g_lin, g_x = self.head.dgrad_ln(_mx(g_head.view(N * T, -1), g_head), st["rstd_h"], mul=t_last)
             else:
-                g_hN = self.head.dgrad(_mx(g_head.view(N * T, -1)))
+                g_hN = self.head.dgrad(_mx(g_head.view(N * T, -1), g_head))
                 g_x, g_lin = self.head_ln.bwd(g_hN, st["rstd_h"], mul2=t_last, want_out=True, want_out2=True)
         else:
-            g_head = ops.head_onehot_grad(cls, st["t_head"].view(N, 1, 1, -1), self.logit_temperature)     # [N,1,1,K]
+            g_head = self._head_grad(cls, functional, st["t_head"].view(N, 1, 1, -1))     # [N,1,1,K]
             g_hN = self.head.dgrad(g_head.view(N, -1))
             g_pool, _ = self.head_ln.bwd(g_hN, st["rstd_h"])
             g_x = (g_pool / T).repeat_interleave(T, dim=0).contiguous()          # gradient of the token mean
@@ -495,7 +566,8 @@ class ViTEngine:
             else:
                 g_h = ops.matmul_nt(_mx(g_v.view(N * T, -1), g_v), blk["wv_t"], track_absmax=False)
                 g_x, g_lin = blk["ln1"].bwd(g_h, rec["rstd1"], addend=g_x1, mul2=t_prev, want_out=bi > 0, want_out2=True)
-            st["blocks"][bi] = None
+            if consume:
+                st["blocks"][bi] = None
             yield
         gp = ops.matmul_nt(_mx(g_lin), self.embed_wt, track_absmax=False)      # [N*T, p*p*cpad] patch-major input gradient
         _, std = self._consts(x.device)
@@ -523,8 +595,7 @@ class ViTEngine:
             wts, contrib = ops.finalize_explanation_patches(gp, st["x"], std, self.patch, add_inverse=st["add_inverse"],
                                                             want_weights=want_weights, want_contrib=True,
                                                             weights_out=outs[0] if outs else None, contrib_out=outs[1] if outs else None)
-        return dict(logits=logits, prediction=pred, explained_class_idx=cls, dynamic_linear_weights=wts,
-                    contribution_map=contrib)
+        return wts, contrib
 
 
 def attach(net) -> ViTEngine:

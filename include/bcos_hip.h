@@ -574,6 +574,30 @@ int bcos_head_rank1_grad(const int64_t* cls, const float* scale, const float* w,
 int bcos_head_rank1_grad_ex(const int64_t* cls, const float* scale, const float* w, const float* row_scale, const float* mul,
                             const float* mul2, const float* gate2, int gate2_from_mul, float* out, float* out2, uint32_t* out_absmax,
                             uint32_t* out2_absmax, int N, int R, int K, int D, float inv_temperature, void* stream);
+/* The start of the explanation pass for a LINEAR FUNCTIONAL of the logits, f = sum_k c_k y_k, instead of one logit.  In explanation mode
+ * the network is linear in the head cotangent (scales, gates and variances are detached, the LogitLayer bias is a constant:
+ * bcos/common.py:163-181), so W_f(x) = sum_k c_k W_k(x) and only this launch knows about the functional -- "why class a rather than b"
+ * (y_a - y_b), the mean-corrected y_t - mean_k y_k of OursRelative (interpretability/explanation_methods/explainers/ours.py:28-33).
+ * Additive entry points of ABI v12: a binding recognises them by the presence of the symbols.
+ *
+ * SPARSE form: bcos_head_rank1_grad_ex with J classes cls [N, J] (int64) and coefficients coef [N, J] (fp32) per image, 1 <= J <= 8:
+ *   v[n, r, :] = sum_{j < J} a_j * w[cls[n, j], :],   a_j = ((inv_temperature / R * scale[n, r, cls[n, j]]) * row_scale[n r]) * coef[n, j]
+ * -- one fp32 chain in ascending j of separately rounded products.  Every output of the _ex form: out = v * mul (mul NULL: v),
+ * out2 = v [* mul2] gated by gate2 > 0 or by the low mantissa bit of mul, both row maxima.  A class outside [0, K) contributes ZERO and
+ * nothing is read out of range.  J = 1 with coef = 1 gives the bits of bcos_head_rank1_grad_ex.
+ * BCOS_E_INVAL: a NULL cls / coef / scale / w / out, N / R / K / D <= 0, D % 4 != 0, J < 1, out2's companions without out2,
+ * gate2_from_mul without mul or with gate2, w / mul / mul2 / gate2 / out / out2 not 16-byte aligned, cls / coef not aligned to their
+ * element.  BCOS_E_NOSUP: J > 8 (use the dense form).  The library never reads device memory. */
+int bcos_head_rankm_grad(const int64_t* cls, const float* coef, int J, const float* scale, const float* w, const float* row_scale,
+                         const float* mul, const float* mul2, const float* gate2, int gate2_from_mul, float* out, float* out2,
+                         uint32_t* out_absmax, uint32_t* out2_absmax, int N, int R, int K, int D, float inv_temperature, void* stream);
+/* DENSE form: bcos_head_onehot_grad with a cotangent row per image, cot [N, K], instead of a one-hot one:
+ *   glin[n, r, k] = (cot[n, k] * scale[n, r, k]) * (inv_temperature / R)      scale [N, R, K] -> glin [N, R, Kp],
+ * Kp = K rounded up to a multiple of 4, the pad columns written as zeros (the input-gradient contraction of the head reads glin with
+ * bcos_tapconv_geom.a_pitch = Kp); out_absmax [N R] or NULL: the bit patterns of the row maxima of |glin| (that contraction's a_absmax).
+ * BCOS_E_INVAL: a NULL cot / scale / glin, N / R / K <= 0, glin not 16-byte aligned, cot / scale / out_absmax not 4-byte aligned. */
+int bcos_head_cotangent_grad(const float* cot, const float* scale, float* glin, uint32_t* out_absmax, int N, int R, int K,
+                             float inv_temperature, void* stream);
 
 /* Row-wise arg-max over logits [N,C] -> idx [N] (int64), val [N]; ties -> lowest index
  * (torch.max semantics used at bcos/common.py:166). */
