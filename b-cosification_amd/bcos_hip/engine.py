@@ -18,16 +18,16 @@ dynamic scale s = |lin| / ||patch|| held constant -- exactly what `.detach()` do
 """
 import math
 import os
-import threading
 from typing import Dict, List, Optional
 
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import ops, passes
 from .functional import LogitFunctional, as_functional
 from .lib import (BCOS_CONV_EPS, BCOS_EPI_FORCE_POW, BCOS_EPI_GATE2_FROM_MUL, BCOS_EPI_MUL_FROM_ACT, BCOS_EPI_SCALE_GATE_LSB,
                   BCOS_NONE, BcosHipError)
+from .passes import _SUBBATCH_MIN, _SUBBATCH_STREAMS, _drive      # noqa: F401  (the sub-batch defaults: bcos_hip/passes.py)
 
 _GATE_TENSOR = bool(os.environ.get("BCOS_GATE_TENSOR"))   # development switch: ReLU gates as tensors, not as the bit in t
 # The multiplier t of conv1 / conv2 of every block (B = 2, own ReLU, no residual) is REBUILT from the kept activation, the patch
@@ -44,67 +44,6 @@ _STORE_T = bool(os.environ.get("BCOS_STORE_T"))
 # therefore only used for layers whose BN shift is small against their BN scale -- max|csh| <= this factor x median|csc| --
 # (the calibrated synthetic networks; real checkpoints with large BN biases keep the stored multipliers).
 _REBUILD_MAX_SHIFT = float(os.environ.get("BCOS_REBUILD_MAX_SHIFT", "0.5"))
-# Images are independent in eval mode: a batch of at least 2 x _SUBBATCH_MIN images is split into _SUBBATCH_STREAMS contiguous
-# sub-batches whose passes are issued on their own HIP streams.  The launches of one sub-batch fill the tails of the other's
-# (a launch ends with most CUs idle while its last tiles finish; 117 + ~15 launches per step) and its HBM-bound launches overlap
-# the other's matrix-bound ones: same-node A/B at ResNet-50 batch 256: 26.13 -> 24.63 ms per step with 2 streams (4: 24.68),
-# results bit-identical (an image's result does not depend on what else is in its batch: test_determinism_and_batch_independence).
-_SUBBATCH_STREAMS = int(os.environ.get("BCOS_SUBBATCH_STREAMS", "2"))
-_SUBBATCH_MIN = int(os.environ.get("BCOS_SUBBATCH_MIN", "32"))
-
-
-def _drive(gen):
-    """run a pass generator to its end and hand back its return value"""
-    try:
-        while True:
-            next(gen)
-    except StopIteration as stop:
-        return stop.value
-
-
-_ISSUING = threading.Lock()        # ops._ARENA is a module global switched per generator resume: ONE pass sequence is issued at a time
-
-
-def _interleave(gens, streams, arenas, device):
-    """Issue the passes of several sub-batches INTERLEAVED: generator i is resumed under stream i and maxima arena i, one block at a
-    time, round-robin.  Issued one whole pass after the other, the second stream's first launch is queued only when the host is done
-    with the first pass -- 4 ms into a ResNet-50 step that takes 23 (scripts/probe/host_bound_probe.py); back-to-back steps hide that
-    behind the previous step, an isolated call does not.  The launches of a pass and their order on its stream are unchanged.
-    Threading: like the reference's `explanation_mode` context (bcos/common.py:347-384 mutates module state) this is single-threaded by
-    design -- the maxima arena is a module global of bcos_hip.ops; a second Python thread entering while a pass sequence is being
-    issued raises instead of corrupting both passes silently.
-    Errors: when one pass generator raises, the others are closed and the caller's stream is ordered behind every side stream BEFORE
-    the exception propagates -- the half-issued launches write into output tensors the caller may free or reuse."""
-    if not _ISSUING.acquire(blocking=False):
-        raise BcosHipError("engine: explain() / forward() re-entered from a second thread while a pass sequence is being issued "
-                           "(the fused plan is single-threaded, like the reference's explanation_mode context)")
-    n = len(gens)
-    results, live = [None] * n, list(range(n))
-    prev = ops._ARENA
-    try:
-        for i in range(n):
-            with torch.cuda.stream(streams[i]):          # (the zero fill of pass i's maxima is ordered on pass i's stream)
-                arenas[i].reset(device)
-        while live:
-            for i in list(live):
-                ops.set_absmax_arena(arenas[i])
-                with torch.cuda.stream(streams[i]):
-                    try:
-                        next(gens[i])
-                    except StopIteration as stop:
-                        results[i] = stop.value
-                        live.remove(i)
-    except BaseException:
-        for g in gens:
-            g.close()
-        cur = torch.cuda.current_stream()
-        for st in streams[:n]:
-            cur.wait_stream(st)
-        raise
-    finally:
-        ops.set_absmax_arena(prev)
-        _ISSUING.release()
-    return results
 
 
 def check_occluded_input(x, rects):
@@ -113,11 +52,27 @@ def check_occluded_input(x, rects):
         raise ValueError(f"forward(x, occlude=...): expected ONE 6-channel image [1,6,H,W] (the masks multiply the network input; "
                          f"masking before AddInverse is a different operator), got {tuple(x.shape)}")
     ops.require_device(x, "bcos_hip.engine")
-    if not (torch.is_tensor(rects) and rects.is_cuda and rects.device == x.device and rects.dtype == torch.int32 and rects.dim() == 2
+    if not (torch.is_tensor(rects) and rects.device == x.device and rects.dtype == torch.int32 and rects.dim() == 2      # (x is on a device)
             and rects.shape[1] == 4 and rects.is_contiguous() and rects.shape[0] > 0):
         raise ValueError("forward(x, occlude=...): the mask bank is a contiguous int32 tensor [n, 4] of rectangles on the image's device")
-    x = x.detach()
-    return (x if x.is_contiguous() else x.contiguous()), rects.shape[0]
+    return passes.detached(x), rects.shape[0]
+
+
+def forward_passes(eng, x, occlude=None):
+    """forward(x, occlude=...) of both engines from the engine's forward generator: the head output of the batch x, or of the n occluded
+    copies of the ONE image x (cut where forward() cuts an n-image batch)"""
+    if occlude is None:
+        x = passes.detached(x)
+        n = x.shape[0]
+    else:
+        x, n = check_occluded_input(x, occlude)
+
+    def one(lo, hi):
+        gen = (eng._run_forward_gen(x[lo:hi], keep=False) if occlude is None
+               else eng._run_forward_gen(x, keep=False, occlude=(occlude, lo, hi - lo)))
+        return (yield from gen)[0]
+    parts = eng._passes(x, n, one)
+    return parts[0] if len(parts) == 1 else torch.cat(parts)
 
 
 def _pair(v):
@@ -429,7 +384,7 @@ class ResNetEngine:
         self.subbatch_streams = _SUBBATCH_STREAMS   # 1 = every pass on the caller's stream
         # (three streams, measured on the CLIP image encoder at batch 256: 8 650 / 8 705 against 8 651 / 8 608 images/s with two, same
         #  node -- within the noise; the ViT plan, whose launches are shorter still, does gain: bcos_hip/vit_engine.py)
-        self._side = None                           # (streams, arenas) of the sub-batch passes, created on first use
+        self._side = passes.SideStreams()           # (streams, arenas) of the sub-batch passes, created on first use
         if self.head_kind in ("attnpool", "attn_unpool"):
             self._refresh_attnpool()
 
@@ -718,50 +673,23 @@ class ResNetEngine:
         g_lin = g_v[:, 1:] + g_v[:, :1] / float(H * W)                   # positions + their share of the mean token
         return ops.ensure_absmax(g_lin.reshape(N, H, W, C).contiguous())
 
+    def _prepare(self, device):
+        """everything the passes cache lazily, brought up to date on the current stream (passes.SideStreams.run)"""
+        self._ensure_fresh()
+        self._consts(device)
+
+    def _stream_limit(self, cotangent=None) -> int:
+        return 1 if (cotangent is not None or self.head_kind == "attn_unpool") else self.subbatch_streams
+
+    def _passes(self, x, n, make_gen, cotangent=None):
+        return self._side.run(x.device, n, self._stream_limit(cotangent), make_gen, self._absmax_arena, lambda: self._prepare(x.device))
+
     @torch.no_grad()
     def forward(self, x: torch.Tensor, occlude: Optional[torch.Tensor] = None) -> torch.Tensor:
         """`occlude` (a device bank [n, 4] of int32 rectangles, include/bcos_hip.h): x is ONE 6-channel image [1, 6, H, W] and the result
         the head output [n, ...] of its n occluded copies `x * mask_i` (occlusion.py:80-90) -- the copies are never built: the prepared
         input comes from ops.prep_input_occluded, everything behind it is the plan of an n-image batch, sub-batch streams included."""
-        if occlude is not None:
-            return self._forward_occluded(x, occlude)
-        S = self._n_subbatches(x) if self.head_kind != "attn_unpool" else 1
-        if S > 1:                                  # sub-batches on side streams (see _SUBBATCH_STREAMS)
-            streams, arenas = self._side_for(x, S)
-            cur = torch.cuda.current_stream()
-            x = x.detach()
-            x = x if x.is_contiguous() else x.contiguous()
-            N = x.shape[0]
-            for i in range(S):
-                streams[i].wait_stream(cur)
-            parts = [r[0] for r in _interleave([self._run_forward_gen(x[(N * i) // S:(N * (i + 1)) // S], keep=False) for i in range(S)],
-                                               streams, arenas, x.device)]
-            for st in streams[:S]:
-                cur.wait_stream(st)
-            for t in parts:
-                t.record_stream(cur)
-            return torch.cat(parts)
-        with ops.absmax_arena(self._absmax_arena, x.device):
-            return self._run_forward(x, keep=False)[0]
-
-    def _forward_occluded(self, x, rects):
-        x, n = check_occluded_input(x, rects)
-        S = min(int(self.subbatch_streams), n // _SUBBATCH_MIN) if self.head_kind != "attn_unpool" else 1
-        if S <= 1 or torch.cuda.is_current_stream_capturing():
-            with ops.absmax_arena(self._absmax_arena, x.device):
-                return _drive(self._run_forward_gen(x, keep=False, occlude=(rects, 0, n)))[0]
-        streams, arenas = self._side_for(x, S)
-        cur = torch.cuda.current_stream()
-        for i in range(S):
-            streams[i].wait_stream(cur)
-        cuts = [(n * i) // S for i in range(S + 1)]              # (the cuts of forward() on an n-image batch)
-        parts = [r[0] for r in _interleave([self._run_forward_gen(x, keep=False, occlude=(rects, cuts[i], cuts[i + 1] - cuts[i]))
-                                            for i in range(S)], streams, arenas, x.device)]
-        for st in streams[:S]:
-            cur.wait_stream(st)
-        for t in parts:
-            t.record_stream(cur)
-        return torch.cat(parts)
+        return forward_passes(self, x, occlude)
 
     @torch.no_grad()
     def explain(self, x: torch.Tensor, targets: Optional[torch.Tensor] = None, want_weights: bool = True,
@@ -780,10 +708,21 @@ class ResNetEngine:
         functional = self._checked_functional(x, functional, targets, cotangent)
         if targets is not None and self.head_kind == "gap_fc":
             targets = ops.check_targets(targets, self.head.cout)       # IndexError like the reference's out[0, idx]; negative indices wrap
-        S = self.n_streams(x, cotangent=cotangent)
-        if S > 1:
-            return self._explain_subbatches(x, targets, want_weights, S, gates, functional)
-        return self._explain_one(x, targets, want_weights, gates, cotangent, self._absmax_arena, functional=functional)
+        x = passes.detached(x)
+        outs = None
+        if self.n_streams(x, cotangent=cotangent) > 1:
+            # sub-batches write into ONE set of output tensors and read ONE device copy of the targets; a single pass allocates its
+            # outputs and moves its targets behind its forward, as it always did
+            outs = passes.explanation_outputs(x, want_weights)
+            targets = None if targets is None else targets.to(device=x.device, dtype=torch.int64).contiguous()
+
+        def one(lo, hi):
+            cut = lambda t: None if t is None else t[lo:hi]      # noqa: E731
+            return self._explain_one_gen(x[lo:hi], cut(targets), want_weights,
+                                         None if gates is None else [gt[lo:hi] for gt in gates],       # (replayed ReLU decisions: [N, ...] like the activations)
+                                         cotangent, outs=None if outs is None else (cut(outs[0]), outs[1][lo:hi]),
+                                         functional=None if functional is None else functional[lo:hi].to(x.device))
+        return passes.assemble_explanation(self._passes(x, x.shape[0], one, cotangent), outs)
 
     def n_logits(self) -> int:
         """width of the head output a target index / a functional's cotangent refers to (attention-pool heads: the embedding)"""
@@ -807,64 +746,7 @@ class ResNetEngine:
         in exactly three cases: a `cotangent` callable (it is handed the head output of the whole batch at once), the `attn_unpool`
         head (its output is token-major), and a pass that is being captured into a hipGraph.  Results
         do not depend on the answer: an image's bits are a function of the image alone."""
-        if cotangent is not None or self.head_kind == "attn_unpool":
-            return 1
-        return self._n_subbatches(x)
-
-    def _side_for(self, x, S):
-        """(streams, arenas) of the sub-batch passes on x's device, created on first use.  Everything the passes cache lazily --
-        refreshed layer plans, the attention-pool copies, the mean / std constants -- is brought up to date HERE, on the caller's
-        stream, which every side stream then waits for: no sub-batch reads a cache another one is still producing."""
-        self._ensure_fresh()
-        self._consts(x.device)
-        key = str(x.device)
-        if self._side is None:
-            self._side = {}
-        if key not in self._side or len(self._side[key][0]) < S:
-            self._side[key] = ([torch.cuda.Stream(device=x.device) for _ in range(S)], [ops.AbsmaxArena() for _ in range(S)])
-        return self._side[key]
-
-    def _n_subbatches(self, x) -> int:
-        S = min(int(self.subbatch_streams), x.shape[0] // _SUBBATCH_MIN)      # (fewer streams for batches under S x _SUBBATCH_MIN images)
-        if S <= 1 or not x.is_cuda or torch.cuda.is_current_stream_capturing():
-            return 1
-        return S
-
-    def _explain_subbatches(self, x, targets, want_weights, S, gates=None, functional=None):
-        """explain() of S contiguous sub-batches on S side streams, written into ONE set of output tensors (see
-        _SUBBATCH_STREAMS).  The side streams start behind the caller's stream and the caller's stream waits for them."""
-        streams, arenas = self._side_for(x, S)
-        cur = torch.cuda.current_stream()
-        N, _, H, W = x.shape
-        x = x.detach()
-        x = x if x.is_contiguous() else x.contiguous()
-        wts = torch.empty((N, 6, H, W), device=x.device, dtype=torch.float32) if want_weights else None
-        contrib = torch.empty((N, H, W), device=x.device, dtype=torch.float32)
-        bounds = [(N * i) // S for i in range(S + 1)]
-        tg = None if targets is None else targets.to(device=x.device, dtype=torch.int64).contiguous()
-        gens = []
-        for i in range(S):
-            lo, hi = bounds[i], bounds[i + 1]
-            streams[i].wait_stream(cur)
-            sub_gates = None if gates is None else [gt[lo:hi] for gt in gates]       # (replayed ReLU decisions: [N, ...] like the activations)
-            gens.append(self._explain_one_gen(x[lo:hi], None if tg is None else tg[lo:hi], want_weights, sub_gates, None,
-                                              outs=(wts[lo:hi] if want_weights else None, contrib[lo:hi]),
-                                              functional=None if functional is None else functional[lo:hi].to(x.device)))
-        parts = _interleave(gens, streams, arenas, x.device)
-        for st in streams[:S]:
-            cur.wait_stream(st)
-        res = {}
-        for k in ("logits", "prediction", "explained_class_idx" if functional is None else "functional_value"):
-            ts = [p[k] for p in parts]
-            for t in ts:
-                t.record_stream(cur)             # allocated in a side stream's pool, read by the cat on the caller's stream
-            res[k] = torch.cat(ts)
-        res.update(dynamic_linear_weights=wts, contribution_map=contrib)
-        return res
-
-    def _explain_one(self, x, targets, want_weights, gates, cotangent, arena, outs=None, functional=None):
-        with ops.absmax_arena(arena, x.device):
-            return _drive(self._explain_one_gen(x, targets, want_weights, gates, cotangent, outs, functional))
+        return passes.n_streams(x.shape[0], self._stream_limit(cotangent), x.device)
 
     def _explain_one_gen(self, x, targets, want_weights, gates, cotangent, outs=None, functional=None):
         """forward + input-gradient pass of one (sub-)batch as a generator (yields behind every block of either pass); the caller owns
@@ -902,24 +784,13 @@ class ResNetEngine:
         Returns logits [N,K], contribution_maps [N,T,H,W] and, if requested, dynamic_linear_weights [N,T,6,H,W]."""
         if self.head_kind == "gap_fc":
             targets = ops.check_targets(targets, self.head.cout)
-        with ops.absmax_arena(self._absmax_arena, x.device):
-            logits, st = self._run_forward(x, keep=True)
-            targets = ops.check_targets(targets, logits.shape[1]) if self.head_kind != "gap_fc" else targets
-            tg = targets.to(device=logits.device, dtype=torch.int64)
-            if tg.dim() == 1:
-                tg = tg.view(1, -1).expand(x.shape[0], -1)
-            T = tg.shape[1]
-            maps = torch.empty((x.shape[0], T, st["H"], st["W"]), device=x.device, dtype=torch.float32)
-            wall = torch.empty((x.shape[0], T, 6, st["H"], st["W"]), device=x.device, dtype=torch.float32) if want_weights else None
-            for k in range(T):
-                wts, contrib = self._backward(x, st, tg[:, k].contiguous(), want_weights, consume=(k == T - 1))
-                maps[:, k] = contrib
-                if want_weights:
-                    wall[:, k] = wts
-        out = dict(logits=logits, contribution_maps=maps)
-        if want_weights:
-            out["dynamic_linear_weights"] = wall
-        return out
+
+        def columns(logits):
+            tg = targets if self.head_kind == "gap_fc" else ops.check_targets(targets, logits.shape[1])
+            tg = tg.to(device=logits.device, dtype=torch.int64)
+            return (tg.view(1, -1).expand(x.shape[0], -1) if tg.dim() == 1 else tg).unbind(1)
+        return self._explain_repeated(x, columns, lambda st, cls, last: self._backward(x, st, cls.contiguous(), want_weights, consume=last),
+                                      want_weights)
 
     @torch.no_grad()
     def explain_functionals(self, x: torch.Tensor, functionals, want_weights: bool = False) -> Dict[str, torch.Tensor]:
@@ -930,20 +801,14 @@ class ResNetEngine:
         fs = [self._checked_functional(x, f) for f in functionals]
         if not fs or any(f is None for f in fs):
             raise ValueError("explain_functionals: a non-empty list of LogitFunctional objects")
-        T = len(fs)
-        with ops.absmax_arena(self._absmax_arena, x.device):
-            logits, st = self._run_forward(x, keep=True)
-            maps = torch.empty((x.shape[0], T, st["H"], st["W"]), device=x.device, dtype=torch.float32)
-            wall = torch.empty((x.shape[0], T, 6, st["H"], st["W"]), device=x.device, dtype=torch.float32) if want_weights else None
-            for k, f in enumerate(fs):
-                wts, contrib = self._backward(x, st, None, want_weights, consume=(k == T - 1), functional=f)
-                maps[:, k] = contrib
-                if want_weights:
-                    wall[:, k] = wts
-        out = dict(logits=logits, functional_values=torch.stack([f.value(logits) for f in fs], 1), contribution_maps=maps)
-        if want_weights:
-            out["dynamic_linear_weights"] = wall
+        out = self._explain_repeated(x, lambda logits: fs,
+                                     lambda st, f, last: self._backward(x, st, None, want_weights, consume=last, functional=f), want_weights)
+        out["functional_values"] = torch.stack([f.value(out["logits"]) for f in fs], 1)
         return out
+
+    def _explain_repeated(self, x, make_args, backward, want_weights):
+        with ops.absmax_arena(self._absmax_arena, x.device):
+            return passes.explain_repeated(x, lambda: self._run_forward(x, keep=True), make_args, backward, want_weights)
 
     def _backward(self, x, st, cls, want_weights: bool, consume: bool, g_head=None, outs=None, functional=None):
         return _drive(self._backward_gen(x, st, cls, want_weights, consume, g_head, outs, functional))

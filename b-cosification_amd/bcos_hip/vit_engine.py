@@ -19,9 +19,11 @@ from typing import Dict, Optional
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import ops, passes
+from .engine import _Conv, forward_passes
 from .functional import LogitFunctional, as_functional
 from .lib import BCOS_EPI_FORCE_POW, BCOS_LINEAR_EPS, BcosHipError
+from .passes import _drive
 
 
 class _Lin:
@@ -176,7 +178,6 @@ class ViTEngine:
         stem = getattr(m.to_patch_embedding, "conv_stem", None)
         if stem is not None:
             from bcos.modules.norms.centered_norms import DetachableGroupNorm2d
-            from .engine import _Conv
             mods = list(stem.children())
             if len(mods) % 3:
                 raise BcosHipError("vit engine: conv stem must be (conv, norm, activation) triples")
@@ -211,7 +212,7 @@ class ViTEngine:
         # three sub-batch streams for the token path (ResNets: two): its launches are shorter -- 394 tiles per half-batch GEMM at batch
         # 512 -- and a third stream fills more of their tails: same-node A/B at ViT-Ti batch 512, three pairs: 18.76 / 18.86 / 18.77 ms
         # against 19.23 / 19.29 / 19.14 with two (ResNet-50: no difference).  Fewer streams for batches under 3 x _SUBBATCH_MIN.
-        self.subbatch_streams, self._side = _VIT_SUBBATCH_STREAMS, None
+        self.subbatch_streams, self._side = _VIT_SUBBATCH_STREAMS, passes.SideStreams()
         self.refresh()
 
     def _fingerprint(self):
@@ -284,11 +285,10 @@ class ViTEngine:
 
     # --------------------------------------------------------------------------------------------------------
     def _run_forward(self, x, keep):
-        from .engine import _drive
         return _drive(self._run_forward_gen(x, keep))
 
     def _run_forward_gen(self, x, keep, occlude=None):
-        """the forward pass as a generator (yields behind the embedding and behind every encoder block: engine._interleave);
+        """the forward pass as a generator (yields behind the embedding and behind every encoder block: passes._interleave);
         `occlude` = (bank, first, n): the batch is the n copies of the ONE image x occluded by bank[first:first + n] (forward only)"""
         if x.dim() != 4 or x.shape[1] not in (3, 6):
             raise ValueError(f"expected [N,6,H,W] (or [N,3,H,W] to be AddInverse-encoded), got {tuple(x.shape)}")
@@ -371,89 +371,42 @@ class ViTEngine:
             st.update(rstd_h=rstd_h, t_head=t_head)
         return logits, st
 
-    def _sub_batches(self, x, make_gen, n=None):
-        """Run the pass generator make_gen(lo, hi) for contiguous sub-batches on side streams, their launches issued interleaved
-        (bcos_hip/engine.py: _SUBBATCH_STREAMS, _interleave: images are independent, the sub-batches fill each other's launch tails)
-        or once on the caller's stream."""
-        from .engine import _SUBBATCH_MIN, _drive, _interleave
-        N = x.shape[0] if n is None else n          # (n: the batch is n occluded copies of the one image x)
-        S = min(int(self.subbatch_streams), N // _SUBBATCH_MIN)
-        if S <= 1 or not x.is_cuda or torch.cuda.is_current_stream_capturing():
-            with _absmax_policy(), ops.absmax_arena(self._absmax_arena, x.device):
-                return [_drive(make_gen(0, N))]
-        # everything the passes cache lazily (refreshed plans, constants, the positional-embedding table) is brought up to date here,
-        # on the caller's stream, which every side stream then waits for (ADVICE r03); streams are per device
+    def _prepare(self, x):
+        """everything the passes cache lazily (refreshed plans, constants, the positional-embedding table), brought up to date on the
+        current stream (passes.SideStreams.run)"""
         self._ensure_fresh()
         self._consts(x.device)
         if not self.stem and x.dim() == 4:
             self._posemb(x.shape[2] // self.patch, x.shape[3] // self.patch, x.device)
-        key = str(x.device)
-        if self._side is None:
-            self._side = {}
-        if key not in self._side or len(self._side[key][0]) < S:
-            self._side[key] = ([torch.cuda.Stream(device=x.device) for _ in range(S)], [ops.AbsmaxArena() for _ in range(S)])
-        streams, arenas = self._side[key]
-        cur = torch.cuda.current_stream()
-        for i in range(S):
-            streams[i].wait_stream(cur)
+
+    def _passes(self, x, n, make_gen):
+        """make_gen(lo, hi) over n images as sub-batches on side streams, or once on the caller's (bcos_hip/passes.py: images are
+        independent, the sub-batches fill each other's launch tails)"""
         with _absmax_policy():
-            outs = _interleave([make_gen((N * i) // S, (N * (i + 1)) // S) for i in range(S)], streams, arenas, x.device)
-        for st in streams[:S]:
-            cur.wait_stream(st)
-        for o in outs:
-            for t in (o.values() if isinstance(o, dict) else [o]):
-                if torch.is_tensor(t):
-                    t.record_stream(cur)
-        return outs
+            return self._side.run(x.device, n, self.subbatch_streams, make_gen, self._absmax_arena, lambda: self._prepare(x))
 
     @torch.no_grad()
     def forward(self, x, occlude: Optional[torch.Tensor] = None):
         """`occlude` (a device bank [n, 4] of int32 rectangles): x is ONE image [1, 6, H, W] and the result the logits [n, classes] of
         its n occluded copies (engine.ResNetEngine.forward): prepared by ops.prep_input_occluded, then the plan of an n-image batch."""
-        if occlude is not None:
-            from .engine import check_occluded_input
-            x, n = check_occluded_input(x, occlude)
-
-            def one_occluded(lo, hi):
-                logits, _ = yield from self._run_forward_gen(x, keep=False, occlude=(occlude, lo, hi - lo))
-                return logits
-            outs = self._sub_batches(x, one_occluded, n=n)
-            return outs[0] if len(outs) == 1 else torch.cat(outs)
-        x = x.detach()
-        x = x if x.is_contiguous() else x.contiguous()
-
-        def one(lo, hi):
-            logits, _ = yield from self._run_forward_gen(x[lo:hi], keep=False)
-            return logits
-        outs = self._sub_batches(x, one)
-        return outs[0] if len(outs) == 1 else torch.cat(outs)
+        return forward_passes(self, x, occlude)
 
     @torch.no_grad()
     def explain(self, x, targets: Optional[torch.Tensor] = None, want_weights: bool = True,
                 functional: Optional[LogitFunctional] = None) -> Dict[str, torch.Tensor]:
         """`functional` (bcos_hip.functional.LogitFunctional, instead of `targets`): the pass of a linear functional sum_k c_k y_k of the
         logits (engine.ResNetEngine.explain); the result carries `functional_value` [N] in place of `explained_class_idx`."""
-        x = x.detach()
-        x = x if x.is_contiguous() else x.contiguous()
+        x = passes.detached(x)
         functional = self._checked_functional(x, functional, targets)
         targets = ops.check_targets(targets, self.head.cout)      # IndexError like the reference's out[0, idx]; negative indices wrap
         tg = None if targets is None else targets.to(device=x.device, dtype=torch.int64).contiguous()
-
-        # the two image-sized results of the sub-batches land in ONE pair of tensors (engine.ResNetEngine._explain_subbatches): no
-        # concatenation pass over [N, 6, H, W] behind the step (0.3 ms of a 17.4 ms ViT-Ti step at batch 512)
-        N, _, H, W = x.shape
-        wts = torch.empty((N, 6, H, W), device=x.device, dtype=torch.float32) if want_weights else None
-        contrib = torch.empty((N, H, W), device=x.device, dtype=torch.float32)
+        outs = passes.explanation_outputs(x, want_weights)
 
         def one(lo, hi):
             return self._explain_gen(x[lo:hi], None if tg is None else tg[lo:hi], want_weights,
-                                     outs=(wts[lo:hi] if want_weights else None, contrib[lo:hi]),
+                                     outs=(outs[0][lo:hi] if want_weights else None, outs[1][lo:hi]),
                                      functional=None if functional is None else functional[lo:hi].to(x.device))
-        outs = self._sub_batches(x, one)
-        res = {k: (outs[0][k] if len(outs) == 1 else torch.cat([o[k] for o in outs]))
-               for k in ("logits", "prediction", "explained_class_idx" if functional is None else "functional_value")}
-        res.update(dynamic_linear_weights=wts, contribution_map=contrib)
-        return res
+        return passes.assemble_explanation(self._passes(x, x.shape[0], one), outs)
 
     def n_logits(self) -> int:
         return self.head.cout
@@ -472,31 +425,16 @@ class ViTEngine:
         """ONE forward in explanation mode, then one input-gradient pass per LogitFunctional of `functionals`
         (engine.ResNetEngine.explain_functionals) -> logits [N, K], functional_values [N, T], contribution_maps [N, T, H, W] and, if
         requested, dynamic_linear_weights [N, T, 6, H, W]."""
-        from .engine import _drive
-        x = x.detach()
-        x = x if x.is_contiguous() else x.contiguous()
+        x = passes.detached(x)
         fs = [self._checked_functional(x, f) for f in functionals]
         if not fs or any(f is None for f in fs):
             raise ValueError("explain_functionals: a non-empty list of LogitFunctional objects")
-        N, _, H, W = x.shape
-        nf = len(fs)
-        maps = torch.empty((N, nf, H, W), device=x.device, dtype=torch.float32)
-        wall = torch.empty((N, nf, 6, H, W), device=x.device, dtype=torch.float32) if want_weights else None
         with _absmax_policy(), ops.absmax_arena(self._absmax_arena, x.device):
-            logits, st = self._run_forward(x, keep=True)
-            for k, f in enumerate(fs):
-                wts, contrib = _drive(self._backward_gen(x, st, None, want_weights, functional=f, consume=(k == nf - 1)))
-                maps[:, k] = contrib
-                if want_weights:
-                    wall[:, k] = wts
-        out = dict(logits=logits, functional_values=torch.stack([f.value(logits) for f in fs], 1), contribution_maps=maps)
-        if want_weights:
-            out["dynamic_linear_weights"] = wall
+            out = passes.explain_repeated(x, lambda: self._run_forward(x, keep=True), lambda logits: fs,
+                                          lambda st, f, last: _drive(self._backward_gen(x, st, None, want_weights, functional=f, consume=last)),
+                                          want_weights)
+        out["functional_values"] = torch.stack([f.value(out["logits"]) for f in fs], 1)
         return out
-
-    def _explain(self, x, targets, want_weights):
-        from .engine import _drive
-        return _drive(self._explain_gen(x, targets, want_weights))
 
     def _explain_gen(self, x, targets, want_weights, outs=None, functional=None):
         logits, st = yield from self._run_forward_gen(x, keep=True)

@@ -1353,6 +1353,26 @@ def test_vit_ti_batch512_properties(lib):
     assert rel(sub["dynamic_linear_weights"], ref["dynamic_linear_weights"]) <= 1e-4
 
 
+def test_vit_one_stream_equals_three(lib):
+    """ViT-Ti at 96 images -- the smallest batch that takes all three sub-batch streams -- of 64 x 64 (a 4 x 4 token grid, the smallest
+    the suite runs the token kernels at): forward, explain and explain(functional=) have the same bits on one stream.  (The occluded
+    forwards of both engines and the ResNet forward are compared across stream counts by test_occluded_logits_*.)"""
+    from bcos_hip import synth, vit_engine
+    from bcos_hip.functional import LogitFunctional as LF
+    eng = vit_engine.ViTEngine(synth.build_bcosified_vit("simple_vit_ti_patch16_224").to(DEV).eval())
+    x = synth.synthetic_images(96, seed=5, size=64).to(DEV)
+    f = LF.contrast(torch.arange(96) % 1000, (torch.arange(96) * 7 + 3) % 1000)
+    calls = dict(forward=lambda: dict(logits=eng.forward(x)), explain=lambda: eng.explain(x), functional=lambda: eng.explain(x, functional=f))
+    eng.subbatch_streams = 3
+    several = {k: call() for k, call in calls.items()}
+    eng.subbatch_streams = 1
+    for k, call in calls.items():
+        one = call()
+        assert set(one) == set(several[k])
+        for name, v in one.items():
+            assert v.shape[0] == 96 and torch.equal(v, several[k][name]), (k, name)
+
+
 # ------------------------------------------------------------------------------------------ CLIP RN50 image encoder
 def _golden_clip(golden_dir):
     from bcos_hip import synth
