@@ -26,7 +26,7 @@ import torch.nn as nn
 from . import ops, passes
 from .functional import LogitFunctional, as_functional
 from .lib import (BCOS_CONV_EPS, BCOS_EPI_FORCE_POW, BCOS_EPI_GATE2_FROM_MUL, BCOS_EPI_MUL_FROM_ACT, BCOS_EPI_SCALE_GATE_LSB,
-                  BCOS_NONE, BcosHipError)
+                  BCOS_E_NOSUP, BCOS_NONE, BcosHipError)
 from .passes import _SUBBATCH_MIN, _SUBBATCH_STREAMS, _drive      # noqa: F401  (the sub-batch defaults: bcos_hip/passes.py)
 
 _GATE_TENSOR = bool(os.environ.get("BCOS_GATE_TENSOR"))   # development switch: ReLU gates as tensors, not as the bit in t
@@ -44,6 +44,19 @@ _STORE_T = bool(os.environ.get("BCOS_STORE_T"))
 # therefore only used for layers whose BN shift is small against their BN scale -- max|csh| <= this factor x median|csc| --
 # (the calibrated synthetic networks; real checkpoints with large BN biases keep the stored multipliers).
 _REBUILD_MAX_SHIFT = float(os.environ.get("BCOS_REBUILD_MAX_SHIFT", "0.5"))
+# The block-boundary gradient of an identity-shortcut bottleneck at widths 64 / 256 and the conv3 input gradient below it as ONE launch
+# (ops.boundary_conv3_grad: the [N, H, W, 256] tensor between them never reaches memory; same bits).  BCOS_BOUNDARY_FUSION=0: the pair
+# of launches, for A/B runs; set_boundary_fusion() flips it inside a process.  BOUNDARY_FUSION_CALLS counts the fused launches issued.
+_BOUNDARY_FUSION_ENV = os.environ.get("BCOS_BOUNDARY_FUSION", "1") != "0"
+_BOUNDARY_FUSION = _BOUNDARY_FUSION_ENV
+BOUNDARY_FUSION_CALLS = 0
+
+
+def set_boundary_fusion(on):
+    """True / False: the fused boundary launch on / off; None: back to what BCOS_BOUNDARY_FUSION says.  Returns the previous setting."""
+    global _BOUNDARY_FUSION
+    old, _BOUNDARY_FUSION = _BOUNDARY_FUSION, (_BOUNDARY_FUSION_ENV if on is None else bool(on))
+    return old
 
 
 def check_occluded_input(x, rects):
@@ -817,6 +830,7 @@ class ResNetEngine:
         """Input-gradient pass of logit[cls[n]] for every image n over the state `st` of a kept forward; `consume` frees
         each saved multiplier as soon as it has been used (last / only pass over this state).  `functional` (instead of `cls`): the
         pass of sum_k c_k logit[k] -- only its first launch differs."""
+        global BOUNDARY_FUSION_CALLS
         if functional is not None and self.head_kind == "attnpool":       # a functional over the embedding coordinates: the dense g_emb
             g_head = functional.as_dense(self.n_logits())
         # A "consumer" owns the g_lin tensors of the layers that read some activation X and can therefore
@@ -868,15 +882,38 @@ class ResNetEngine:
                 continue
             # v = d logit / d out_b;  G_main = v * t_last (bn scale, ReLU gate and s of the block's last conv),
             # G_sc = v * gate(out_b) [* t_d]  for the shortcut
-            with ops.image_range_reader(blk.convs[-1].reads_image_range):
-                G_main, G_sc = consumer.run(H, W, t_main=rec["ts"][-1], td=rec["td"], gated=rec["gated"], gate_t=rec["gate_t"],
-                                            track=blk.convs[-1].k_dgrad >= ops.F16X2_MIN_K,
-                                            track2=blk.shortcut is not None and blk.shortcut.k_dgrad >= ops.F16X2_MIN_K)
-            if consume:
-                rec["ts"][-1] = rec["td"] = rec["gate_t"] = None
-            gl = G_main
             convs = blk.convs
-            for ci in range(len(convs) - 1, 0, -1):
+            fused = _boundary_fusable(consumer, blk, rec, H, W)
+            if fused:
+                # the boundary launch and conv3's input gradient in one: gl is already the gradient behind conv3, times conv2's multiplier
+                t2 = rec["ts"][-2]
+                t2kw = dict(mul_norm=t2.norm, mul_csc=t2.ch_scale, mul_csh=t2.ch_shift) if isinstance(t2, _ActScale) else {}
+                try:
+                    with ops.image_range_reader(convs[-2].reads_image_range):
+                        gl, G_sc = ops.boundary_conv3_grad(consumer.g_main, consumer.conv.dgrad.classes[0][8], consumer.g_sc, rec["ts"][-1],
+                                                           convs[-1].dgrad.classes[0][8], t2.act if isinstance(t2, _ActScale) else t2,
+                                                           mul2=rec["td"], track_absmax=convs[-2].k_dgrad >= ops.F16X2_MIN_K,
+                                                           track_absmax2=blk.shortcut is not None and blk.shortcut.k_dgrad >= ops.F16X2_MIN_K,
+                                                           **t2kw)
+                except BcosHipError as err:
+                    # (what _boundary_fusable cannot see from here, e.g. a misaligned view: the call refuses before it launches
+                    #  anything, and the pair of launches takes the site as it always did)
+                    if err.code != BCOS_E_NOSUP:
+                        raise
+                    fused = False
+            if fused:
+                BOUNDARY_FUSION_CALLS += 1
+                if consume:
+                    rec["ts"][-1] = rec["td"] = rec["gate_t"] = rec["tw"][-1] = rec["ts"][-2] = None
+            else:
+                with ops.image_range_reader(convs[-1].reads_image_range):
+                    G_main, G_sc = consumer.run(H, W, t_main=rec["ts"][-1], td=rec["td"], gated=rec["gated"], gate_t=rec["gate_t"],
+                                                track=convs[-1].k_dgrad >= ops.F16X2_MIN_K,
+                                                track2=blk.shortcut is not None and blk.shortcut.k_dgrad >= ops.F16X2_MIN_K)
+                if consume:
+                    rec["ts"][-1] = rec["td"] = rec["gate_t"] = None
+                gl = G_main
+            for ci in range(len(convs) - (2 if fused else 1), 0, -1):
                 h, w = rec["hws"][ci]
                 gl = convs[ci].expand(gl, rec["tw"][ci])          # (MaxOut layers: to the contraction's width; anything else: as is)
                 if consume:
@@ -923,6 +960,33 @@ class ResNetEngine:
                                                 weights_out=outs[0] if outs is not None else None,
                                                 contrib_out=outs[1] if outs is not None else None)
         return wts, contrib
+
+
+def _boundary_fusable(consumer, blk, rec, H, W) -> bool:
+    """May ops.boundary_conv3_grad stand in for consumer.run(...) and the input gradient of blk's last conv?  The reader above is a plain
+    conv1 256 -> 64 with the identity shortcut beside it; `blk` (fused, not hybrid) ends in a 1 x 1 conv 64 -> 256 with no pool in front,
+    its ReLU gate in the low bit of the stored multiplier; no MaxOut, B = 2, f16x2 contraction with the maxima of g_main at hand, both
+    weight banks with their pre-split images, contiguous tensors below the 2 GiB of the kernel's 32-bit offsets.  (The call's own
+    refusals are mirrored here; one that is met anyway -- BCOS_E_NOSUP -- sends the site to the pair of launches too.)"""
+    if not _BOUNDARY_FUSION or type(consumer) is not _Consumer or not isinstance(consumer.conv, _Conv) or len(blk.convs) < 2:
+        return False
+    c1, c3 = consumer.conv, blk.convs[-1]
+    t3, t2 = rec["ts"][-1], rec["ts"][-2]
+    g1 = consumer.g_main
+    t2_parts = [t2.act, t2.norm] if isinstance(t2, _ActScale) else [t2]
+    return bool(consumer.shortcut_conv is None and consumer.g_sc is not None and c1.cin == 256 and c1.cout_all == 64
+                and c3.cin == 64 and c3.cout_all == 256 and c1.dgrad.pointwise and c3.dgrad.pointwise
+                and c1.max_out == 1 and c3.max_out == 1 and c1.b == 2.0 and c3.b == 2.0 and not blk.pool
+                and rec["gated"] and rec["gate_t"] is None and torch.is_tensor(t3)
+                and (rec["td"] is None or (torch.is_tensor(rec["td"]) and tuple(rec["td"].shape) == tuple(t3.shape) and rec["td"].is_contiguous()))
+                and (torch.is_tensor(t2) or isinstance(t2, _ActScale))
+                and tuple(rec["hws"][-1]) == (H, W) and tuple(consumer.g_main.shape[1:3]) == (H, W)
+                and tuple(consumer.g_sc.shape) == tuple(t3.shape) and consumer.g_sc.is_contiguous()
+                and g1.shape[0] * H * W * 256 * 4 < 2 ** 31                          # (the widest tensors, [M, 256] fp32)
+                and g1.is_contiguous() and t3.is_contiguous() and all(torch.is_tensor(t) and t.is_contiguous() for t in t2_parts)
+                and ops.presplit_static(c1.dgrad.classes[0][8]) and ops.presplit_static(c3.dgrad.classes[0][8])
+                and _l_mode() == "f16x2" and ops.F16X2_MIN_K <= 64 and ops.absmax_of(g1) is not None
+                and ops.absmax_of(g1).numel() == g1.shape[0] * H * W)
 
 
 class _HeadConv:

@@ -19,7 +19,7 @@ LIB_PATH = Path(os.environ["BCOS_HIP_LIB"]) if os.environ.get("BCOS_HIP_LIB") el
 CSRC = PKG_ROOT / "csrc"
 INCLUDE = REPO_ROOT / "include"
 SOURCES = ["bcos_tapconv.hip", "bcos_skinny.hip", "bcos_elementwise.hip", "bcos_vit.hip", "bcos_render.hip", "bcos_train.hip",
-           "bcos_agc.hip", "bcos_occlusion.hip", "bcos_head.hip", "bcos_abi.hip"]
+           "bcos_agc.hip", "bcos_occlusion.hip", "bcos_head.hip", "bcos_boundary.hip", "bcos_abi.hip"]
 
 BCOS_NONE, BCOS_CONV_EPS, BCOS_LINEAR_EPS = 0, 1, 2
 BCOS_EPI_NORM_ONLY = 1
@@ -77,6 +77,14 @@ class AgcTensor(C.Structure):
 class TapconvRoute(C.Structure):
     """include/bcos_hip.h: bcos_tapconv_route"""
     _fields_ = [(n, C.c_int32) for n in ("route", "epi_kind", "norm", "loop", "bm", "bn", "chunks", "ch_pass")]
+
+
+class BoundaryConv3(C.Structure):
+    """include/bcos_hip.h: bcos_boundary_conv3"""
+    _fields_ = [(n, C.c_void_p) for n in (
+        "g1", "g1_absmax", "w1_f16x2", "addend", "t3", "mul2", "out2", "out2_absmax", "w3_f16x2", "t2", "mul_norm", "mul_csc", "mul_csh",
+        "g3", "g3_absmax", "g3_imgmax", "g3_imgmin_c")] + [(n, C.c_int32) for n in (
+        "N", "PQ", "C1", "C4", "kh", "kw", "stride", "contraction")] + [("b", C.c_float)]
 
 
 LOOP_NAMES = ("f32", "bf16x3", "bf16x3_presplit", "f16x2_regs", "f16x2_dma", "f16x2_patch")      # include/bcos_hip.h: BCOS_LOOP_*
@@ -179,6 +187,7 @@ SIGNATURES = {
     "bcos_agc_clip": (C.c_int, [C.POINTER(AgcTensor), _I, _F, _F, _P]),
     "bcos_prep_input_occluded": (C.c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "bcos_occlusion_accumulate": (C.c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "bcos_boundary_conv3_grad": (C.c_int, [C.POINTER(BoundaryConv3), _P]),
 }
 
 _lib = None

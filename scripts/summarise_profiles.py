@@ -6,8 +6,8 @@ import csv, glob, json, os, shutil, sys
 
 out, summ, tag = sys.argv[1:4]
 STEPS_PROFILED = 3          # --steps 2 --warmup 1
-KERNELS = ("tapconv_kernel", "tappatch_kernel", "skinny_kernel", "skinny_group_kernel")     # the contraction launches bench.py brackets with HIP events
-LAUNCHES_PER_STEP = 116     # ResNet-50 forward + explanation: 54 forward + 62 input-gradient launches (stem gradient fused; the head gradient is a streaming launch since the end of round 5: 117 before)
+KERNELS = ("tapconv_kernel", "tappatch_kernel", "skinny_kernel", "skinny_group_kernel", "boundary_conv3_kernel")     # the contraction launches bench.py brackets with HIP events
+LAUNCHES_PER_STEP = 114     # ResNet-50 forward + explanation: 54 forward + 60 input-gradient launches (stem gradient fused; the head gradient is a streaming launch since the end of round 5: 117 before; the two block boundaries of stage 1 are one launch each with the conv3 gradient below them, csrc/bcos_boundary.hip: 116 before, and 116 with BCOS_BOUNDARY_FUSION=0)
 
 
 def find(d, suffix):
