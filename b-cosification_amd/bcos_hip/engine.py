@@ -71,18 +71,42 @@ def check_occluded_input(x, rects):
     return passes.detached(x), rects.shape[0]
 
 
-def forward_passes(eng, x, occlude=None):
-    """forward(x, occlude=...) of both engines from the engine's forward generator: the head output of the batch x, or of the n occluded
-    copies of the ONE image x (cut where forward() cuts an n-image batch)"""
-    if occlude is None:
+def check_perturbed_input(x, plan):
+    """forward(x, perturb=plan) of both engines: contiguous 6-channel device images [B,6,H,W] and a plan (bcos_hip.perturbation.PerturbPlan:
+    scores [B, H*W], thr [B, K], descending, K) on their device; -> (x, B * K)"""
+    if x.dim() != 4 or x.shape[1] != 6:
+        raise ValueError(f"forward(x, perturb=...): expected 6-channel images [B,6,H,W] (pixels are removed from the network input; "
+                         f"masking before AddInverse is a different operator), got {tuple(x.shape)}")
+    ops.require_device(x, "bcos_hip.engine")
+    B, _, H, W = x.shape
+    scores, thr, K = getattr(plan, "scores", None), getattr(plan, "thr", None), getattr(plan, "K", None)
+    if not (torch.is_tensor(scores) and scores.device == x.device and scores.dtype == torch.float32 and tuple(scores.shape) == (B, H * W)
+            and scores.is_contiguous() and torch.is_tensor(thr) and thr.device == x.device and thr.dtype == torch.int64
+            and isinstance(K, int) and K > 0 and tuple(thr.shape) == (B, K) and thr.is_contiguous() and hasattr(plan, "descending")):
+        raise ValueError("forward(x, perturb=...): the plan holds contiguous scores [B, H*W] (float32) and thr [B, K] (int64, from "
+                         "ops.perturb_select) on the images' device, `descending` and K")
+    return passes.detached(x), B * K
+
+
+def forward_passes(eng, x, occlude=None, perturb=None):
+    """forward(x, occlude=... / perturb=...) of both engines from the engine's forward generator: the head output of the batch x, of the n
+    occluded copies of the ONE image x, or of the B * K perturbed copies of the images x (cut where forward() cuts an n-image batch)"""
+    if occlude is not None and perturb is not None:
+        raise ValueError("forward(x, occlude=..., perturb=...): one of the two at a time")
+    if perturb is not None:
+        x, n = check_perturbed_input(x, perturb)
+    elif occlude is None:
         x = passes.detached(x)
         n = x.shape[0]
     else:
         x, n = check_occluded_input(x, occlude)
 
     def one(lo, hi):
-        gen = (eng._run_forward_gen(x[lo:hi], keep=False) if occlude is None
-               else eng._run_forward_gen(x, keep=False, occlude=(occlude, lo, hi - lo)))
+        if perturb is not None:
+            gen = eng._run_forward_gen(x, keep=False, perturb=(perturb, lo, hi - lo))
+        else:
+            gen = (eng._run_forward_gen(x[lo:hi], keep=False) if occlude is None
+                   else eng._run_forward_gen(x, keep=False, occlude=(occlude, lo, hi - lo)))
         return (yield from gen)[0]
     parts = eng._passes(x, n, one)
     return parts[0] if len(parts) == 1 else torch.cat(parts)
@@ -482,10 +506,11 @@ class ResNetEngine:
     def _run_forward(self, x: torch.Tensor, keep: bool, gates=None):
         return _drive(self._run_forward_gen(x, keep, gates))
 
-    def _run_forward_gen(self, x: torch.Tensor, keep: bool, gates=None, occlude=None):
+    def _run_forward_gen(self, x: torch.Tensor, keep: bool, gates=None, occlude=None, perturb=None):
         """The forward pass as a generator: it yields (nothing) behind the stem and behind every block, so that the passes of several
         sub-batches can be ISSUED interleaved (see _interleave); its return value is (head output, kept state).
-        `occlude` = (bank, first, n): the batch is the n copies of the ONE image x occluded by bank[first:first + n] (forward only)."""
+        `occlude` = (bank, first, n): the batch is the n copies of the ONE image x occluded by bank[first:first + n] (forward only).
+        `perturb` = (plan, first, n): the batch is copies [first, first + n) of the perturbed copies of the images x (forward only)."""
         if x.dim() != 4 or x.shape[1] not in (3, 6):
             raise ValueError(f"expected [N,6,H,W] (or [N,3,H,W] to be AddInverse-encoded), got {tuple(x.shape)}")
         ops.require_device(x, "bcos_hip.engine")
@@ -494,7 +519,10 @@ class ResNetEngine:
         x = x if x.is_contiguous() else x.contiguous()
         mean, std = self._consts(x.device)
         add_inverse = x.shape[1] == 3
-        if occlude is None:
+        if perturb is not None:
+            xn = ops.prep_input_perturbed(x, perturb[0].scores, perturb[0].thr, mean, std, descending=perturb[0].descending,
+                                          first=perturb[1], n=perturb[2], cpad=8, want_absmax=True)
+        elif occlude is None:
             xn = ops.prep_input(x, mean, std, cpad=8, add_inverse=add_inverse, want_absmax=True)
         else:
             xn = ops.prep_input_occluded(x, occlude[0], mean, std, first=occlude[1], n=occlude[2], cpad=8, want_absmax=True)
@@ -698,11 +726,14 @@ class ResNetEngine:
         return self._side.run(x.device, n, self._stream_limit(cotangent), make_gen, self._absmax_arena, lambda: self._prepare(x.device))
 
     @torch.no_grad()
-    def forward(self, x: torch.Tensor, occlude: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, occlude: Optional[torch.Tensor] = None, perturb=None) -> torch.Tensor:
         """`occlude` (a device bank [n, 4] of int32 rectangles, include/bcos_hip.h): x is ONE 6-channel image [1, 6, H, W] and the result
         the head output [n, ...] of its n occluded copies `x * mask_i` (occlusion.py:80-90) -- the copies are never built: the prepared
-        input comes from ops.prep_input_occluded, everything behind it is the plan of an n-image batch, sub-batch streams included."""
-        return forward_passes(self, x, occlude)
+        input comes from ops.prep_input_occluded, everything behind it is the plan of an n-image batch, sub-batch streams included.
+        `perturb` (bcos_hip.perturbation.PerturbPlan: scores [B, H*W], thr [B, K], descending, K): x is [B, 6, H, W] and the result the
+        head output [B * K, ...], image-major, of the copies with the first k_j pixels of every image's ranking removed -- prepared by
+        ops.prep_input_perturbed, then the plan of a B * K-image batch, cut along the copy index.  Not together with `occlude`."""
+        return forward_passes(self, x, occlude, perturb)
 
     @torch.no_grad()
     def explain(self, x: torch.Tensor, targets: Optional[torch.Tensor] = None, want_weights: bool = True,

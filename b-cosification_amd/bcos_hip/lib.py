@@ -19,7 +19,7 @@ LIB_PATH = Path(os.environ["BCOS_HIP_LIB"]) if os.environ.get("BCOS_HIP_LIB") el
 CSRC = PKG_ROOT / "csrc"
 INCLUDE = REPO_ROOT / "include"
 SOURCES = ["bcos_tapconv.hip", "bcos_skinny.hip", "bcos_elementwise.hip", "bcos_vit.hip", "bcos_render.hip", "bcos_train.hip",
-           "bcos_agc.hip", "bcos_occlusion.hip", "bcos_head.hip", "bcos_boundary.hip", "bcos_abi.hip"]
+           "bcos_agc.hip", "bcos_occlusion.hip", "bcos_perturb.hip", "bcos_head.hip", "bcos_boundary.hip", "bcos_abi.hip"]
 
 BCOS_NONE, BCOS_CONV_EPS, BCOS_LINEAR_EPS = 0, 1, 2
 BCOS_EPI_NORM_ONLY = 1
@@ -188,6 +188,10 @@ SIGNATURES = {
     "bcos_prep_input_occluded": (C.c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "bcos_occlusion_accumulate": (C.c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "bcos_boundary_conv3_grad": (C.c_int, [C.POINTER(BoundaryConv3), _P]),
+    "bcos_perturb_select_ws_bytes": (C.c_int, [_I, _L, _I, C.POINTER(C.c_int64)]),
+    "bcos_perturb_select": (C.c_int, [_P, _P, _I, _P, _P, _L, _I, _L, _I, _P]),
+    "bcos_prep_input_perturbed": (C.c_int, [_P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "bcos_class_scores": (C.c_int, [_P, _P, _I, _I, _P, _L, _I, _P]),
 }
 
 _lib = None
@@ -212,6 +216,9 @@ def build(force: bool = False, verbose: bool = False) -> Path:
     # (-DBCOS_TAPCONV_PART=k selects which kernel instantiations a slice carries) because its ~30 kernels dominate the build
     objdir = LIB_PATH.parent / "obj"
     objdir.mkdir(parents=True, exist_ok=True)
+    # no -ffast-math and no -fno-hip-fp32-correctly-rounded-divide-sqrt, here or in BCOS_HIPCC_FLAGS of a product build: the rounding
+    # bounds include/bcos_hip.h states (bcos_class_scores) and the bit-equal prepared inputs count on IEEE division and on the
+    # library expf
     flags = ["--offload-arch=gfx950", "-O3", "-std=c++20", "-fPIC", f"-I{INCLUDE}", f"-I{CSRC}"]
     flags += os.environ.get("BCOS_HIPCC_FLAGS", "").split()
     jobs = []

@@ -1150,6 +1150,121 @@ def occlusion_accumulate(org, pert, rects, H, W, targets=None, only_positive=Fal
     return out
 
 
+PERTURB_MAX_COUNTS = 64            # include/bcos_hip.h: BCOS_PERTURB_MAX_COUNTS
+_PERTURB_WS = {}                   # (device, stream) -> workspace of perturb_select (launches of one stream run in order: one buffer)
+
+
+def _perturb_workspace(nbytes: int, device, stream) -> torch.Tensor:
+    key = (device.index, stream.value)
+    buf = _PERTURB_WS.get(key)
+    if buf is None or buf.numel() * 8 < nbytes:
+        buf = torch.empty(max((int(nbytes) + 7) // 8, 1 << 15), device=device, dtype=torch.int64)
+        _PERTURB_WS[key] = buf
+    return buf
+
+
+def _pixel_scores(scores, what):
+    if not (torch.is_tensor(scores) and scores.dtype == torch.float32 and scores.dim() == 2 and scores.is_contiguous() and scores.numel() > 0):
+        raise BcosHipError(f"{what}: the pixel scores are a contiguous float32 tensor [B, H*W]")
+    return scores
+
+
+def _thresholds(thr, B, what):
+    if not (torch.is_tensor(thr) and thr.dtype == torch.int64 and thr.dim() == 2 and thr.is_contiguous() and thr.shape[0] == B and thr.shape[1] > 0):
+        raise BcosHipError(f"{what}: the thresholds are a contiguous int64 tensor [{B}, K] (the uint64 bit patterns of perturb_select)")
+    return thr
+
+
+def perturb_select(scores, counts, descending=False):
+    """scores [B, H*W] (device), counts (K removal counts, integers in [0, H*W]; any order, repeats allowed) -> thr [B, K]: an int64
+    tensor holding the uint64 bit patterns thr_b(counts[j]) of the ranking defined in include/bcos_hip.h (bcos_perturb_select): pixel p
+    of image b is among the first counts[j] of its ranking iff key64_b(p) < thr[b, j] as unsigned numbers.  `descending`: the most
+    important (highest-scoring) pixels come first.  Exact and reproducible; nothing is read back."""
+    lib = _l.load()
+    _pixel_scores(scores, "perturb_select")
+    B, HW = scores.shape
+    try:
+        ks = [int(k) for k in counts]
+        if any(k != c for k, c in zip(ks, counts)):
+            raise ValueError
+    except (TypeError, ValueError):
+        raise BcosHipError("perturb_select: the counts are a sequence of integers") from None
+    K = len(ks)
+    if not 1 <= K <= PERTURB_MAX_COUNTS:
+        raise BcosHipError(f"perturb_select: between 1 and {PERTURB_MAX_COUNTS} removal counts per call, got {K}")
+    if min(ks) < 0 or max(ks) > HW:
+        raise BcosHipError(f"perturb_select: a removal count outside [0, {HW}]: {ks}")
+    if not scores.is_cuda:
+        raise BcosHipError(f"perturb_select: expected a HIP device tensor, got device={scores.device} (no CPU implementation in this package)")
+    need = C.c_int64(0)
+    _l.check(lib.bcos_perturb_select_ws_bytes(B, HW, K, C.byref(need)), "bcos_perturb_select_ws_bytes")
+    st = _stream()
+    ws = _perturb_workspace(need.value, scores.device, st)
+    thr = torch.empty((B, K), device=scores.device, dtype=torch.int64)
+    host = (C.c_int32 * K)(*ks)
+    _l.check(lib.bcos_perturb_select(_dev(scores, "scores"), C.cast(host, C.c_void_p), int(bool(descending)), C.c_void_p(thr.data_ptr()),
+                                     C.c_void_p(ws.data_ptr()), ws.numel() * 8, B, HW, K, st), "bcos_perturb_select")
+    return thr
+
+
+def prep_input_perturbed(x_nchw, scores, thr, mean6, std6, descending=False, first=0, n=None, cpad=8, want_absmax=False):
+    """The prepared input [n, H, W, cpad] of copies [first, first + n) of the B * K perturbed copies of x_nchw [B, 6, H, W] (image-major:
+    copy b * K + j is image b without the pixels of key64 < thr[b, j]): what prep_input returns for the materialised copies, bit for
+    bit, from one launch that never stores them (include/bcos_hip.h: bcos_prep_input_perturbed).  scores [B, H*W] and thr [B, K] are
+    what perturb_select took and returned, `descending` as given there."""
+    lib = _l.load()
+    _pixel_scores(scores, "prep_input_perturbed")
+    if x_nchw.dim() != 4 or x_nchw.shape[1] != 6:
+        raise BcosHipError(f"prep_input_perturbed: 6-channel images [B, 6, H, W] (masking before AddInverse is another operator), "
+                           f"got {tuple(x_nchw.shape)}")
+    B, Cx, H, W = x_nchw.shape
+    if tuple(scores.shape) != (B, H * W):
+        raise BcosHipError(f"prep_input_perturbed: scores {tuple(scores.shape)} for images {tuple(x_nchw.shape)}: expected [{B}, {H * W}]")
+    _thresholds(thr, B, "prep_input_perturbed")
+    K = thr.shape[1]
+    n = B * K - first if n is None else int(n)
+    if first < 0 or n <= 0 or first + n > B * K:
+        raise BcosHipError(f"prep_input_perturbed: copies [{first}, {first + n}) of {B} x {K} = {B * K}")
+    if not x_nchw.is_cuda or scores.device != x_nchw.device or thr.device != x_nchw.device:
+        raise BcosHipError(f"prep_input_perturbed: the scores are on {scores.device}, the thresholds on {thr.device}, the images on {x_nchw.device}")
+    out = torch.empty((n, H, W, cpad), device=x_nchw.device, dtype=torch.float32)
+    am = _fused_absmax(out, want_absmax)
+    _l.check(lib.bcos_prep_input_perturbed(_dev(x_nchw, "x"), _dev(scores, "scores"), C.c_void_p(thr.data_ptr()), int(bool(descending)),
+                                           _dev(out, "out"), _dev(mean6, "mean"), _dev(std6, "std"),
+                                           C.c_void_p(am.data_ptr()) if am is not None else None, B, K, int(first), n, Cx, H, W, cpad, 0,
+                                           _stream()), "bcos_prep_input_perturbed")
+    return out
+
+
+CLASS_SCORE_MODES = {"logit": 0, "sigmoid": 1, "softmax": 2}
+
+
+def class_scores(logits, targets, group=1, mode="logit"):
+    """logits [R, CL] (device), targets (R / group class indices: the `group` consecutive rows of an image share its class) -> [R]: the
+    class's logit, sigmoid (BcosMixin.to_probabilities) or softmax over the row (include/bcos_hip.h: bcos_class_scores, with the
+    rounding bounds of the last two).  `targets`: a sequence / tensor of class indices, validated and wrapped on the host like every
+    explained class -- or an int32 tensor on the logits' device, taken as it is (a class outside the logits then yields NaN)."""
+    lib = _l.load()
+    if mode not in CLASS_SCORE_MODES:
+        raise BcosHipError(f"class_scores: mode must be one of {sorted(CLASS_SCORE_MODES)}, got {mode!r}")
+    if not (torch.is_tensor(logits) and logits.dim() == 2 and logits.numel() > 0):
+        raise BcosHipError("class_scores: logits [rows, classes]")
+    R, CL = logits.shape
+    group = int(group)
+    if group <= 0 or R % group:
+        raise BcosHipError(f"class_scores: {R} rows are not a multiple of group = {group}")
+    if torch.is_tensor(targets) and targets.dtype == torch.int32 and targets.device == logits.device and targets.is_cuda:
+        tg = targets.reshape(-1).contiguous()
+    else:
+        tg = check_targets(targets, CL, "class_scores: targets").reshape(-1).to(device=logits.device, dtype=torch.int32).contiguous()
+    if tg.numel() != R // group:
+        raise BcosHipError(f"class_scores: {tg.numel()} targets for {R} rows in groups of {group}")
+    out = torch.empty((R,), device=logits.device, dtype=torch.float32)
+    _l.check(lib.bcos_class_scores(_dev(logits, "logits"), C.c_void_p(tg.data_ptr()), group, CLASS_SCORE_MODES[mode], _dev(out, "out"),
+                                   R, CL, _stream()), "bcos_class_scores")
+    return out
+
+
 def finalize_explanation(gxn, x_nchw, std6, add_inverse=False, want_weights=True, want_contrib=True, weights_out=None, contrib_out=None):
     """`weights_out` / `contrib_out`: write into these [N,6,H,W] / [N,H,W] tensors (slices of a larger batch) instead of new ones."""
     lib = _l.load()

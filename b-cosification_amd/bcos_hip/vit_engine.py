@@ -287,9 +287,10 @@ class ViTEngine:
     def _run_forward(self, x, keep):
         return _drive(self._run_forward_gen(x, keep))
 
-    def _run_forward_gen(self, x, keep, occlude=None):
+    def _run_forward_gen(self, x, keep, occlude=None, perturb=None):
         """the forward pass as a generator (yields behind the embedding and behind every encoder block: passes._interleave);
-        `occlude` = (bank, first, n): the batch is the n copies of the ONE image x occluded by bank[first:first + n] (forward only)"""
+        `occlude` = (bank, first, n): the batch is the n copies of the ONE image x occluded by bank[first:first + n] (forward only);
+        `perturb` = (plan, first, n): the batch is copies [first, first + n) of the perturbed copies of the images x (forward only)"""
         if x.dim() != 4 or x.shape[1] not in (3, 6):
             raise ValueError(f"expected [N,6,H,W] (or [N,3,H,W] to be AddInverse-encoded), got {tuple(x.shape)}")
         ops.require_device(x, "bcos_hip.vit_engine")
@@ -300,7 +301,11 @@ class ViTEngine:
         p = self.patch
         mean, std = self._consts(x.device)
         add_inverse = x.shape[1] == 3
-        if occlude is None:
+        if perturb is not None:
+            N = perturb[2]
+            xn = ops.prep_input_perturbed(x, perturb[0].scores, perturb[0].thr, mean, std, descending=perturb[0].descending,
+                                          first=perturb[1], n=N, cpad=8, want_absmax=_F16X2)
+        elif occlude is None:
             xn = ops.prep_input(x, mean, std, cpad=8, add_inverse=add_inverse, want_absmax=_F16X2)     # K = 2048 patch embedding
         else:
             N = occlude[2]
@@ -386,10 +391,12 @@ class ViTEngine:
             return self._side.run(x.device, n, self.subbatch_streams, make_gen, self._absmax_arena, lambda: self._prepare(x))
 
     @torch.no_grad()
-    def forward(self, x, occlude: Optional[torch.Tensor] = None):
+    def forward(self, x, occlude: Optional[torch.Tensor] = None, perturb=None):
         """`occlude` (a device bank [n, 4] of int32 rectangles): x is ONE image [1, 6, H, W] and the result the logits [n, classes] of
-        its n occluded copies (engine.ResNetEngine.forward): prepared by ops.prep_input_occluded, then the plan of an n-image batch."""
-        return forward_passes(self, x, occlude)
+        its n occluded copies (engine.ResNetEngine.forward): prepared by ops.prep_input_occluded, then the plan of an n-image batch.
+        `perturb` (bcos_hip.perturbation.PerturbPlan): x is [B, 6, H, W] and the result the logits [B * K, classes], image-major, of its
+        perturbed copies (engine.ResNetEngine.forward): prepared by ops.prep_input_perturbed.  Not together with `occlude`."""
+        return forward_passes(self, x, occlude, perturb)
 
     @torch.no_grad()
     def explain(self, x, targets: Optional[torch.Tensor] = None, want_weights: bool = True,

@@ -927,6 +927,68 @@ typedef struct bcos_boundary_conv3 {
 } bcos_boundary_conv3;
 int bcos_boundary_conv3_grad(const bcos_boundary_conv3* args, void* stream);
 
+/* -- pixel perturbation (deletion curves; additive entry points of ABI v12) ------------------------------------------------- */
+/* An image's HW = H * W pixels are ranked by a score s (fp32, one per pixel p = h * W + w) and the first k of the ranking are REMOVED:
+ * all six channels of the [r,g,b,1-r,1-g,1-b] network input are set to 0 there, as inside an Occlusion rectangle.  THE RANKING, stated
+ * here once:
+ *   m(s)   = bits(s) ^ (bits(s) >> 31 ? 0xFFFFFFFF : 0x80000000)   the usual monotone map of fp32 onto uint32: -0.0 sorts below +0.0,
+ *            -inf lowest, +inf above every finite value, and a NaN orders by its bit pattern (sign bit clear: above +inf; set: below
+ *            -inf).  The library never reads device memory on the host, so it cannot refuse NaNs: they are ranked like this.
+ *   key32  = m(s) for "least important first" (descending == 0), ~m(s) for "most important first" (descending != 0);
+ *   key64  = (uint64)key32 << 32 | p: the HW keys of an image are distinct, ties of key32 break by ascending p in EITHER order;
+ *   thr(k) = the k-th smallest key64 (0-based) for 0 <= k < HW, UINT64_MAX for k = HW;
+ *   copy j of image b removes pixel p iff key64_b(p) < thr_b(k_j): exactly k_j pixels, the first k_j of a stable sort by key32. */
+#define BCOS_PERTURB_MAX_COUNTS 64
+
+/* Workspace of bcos_perturb_select in bytes.  BCOS_E_INVAL: bytes NULL, B outside [1, 65535], HW outside [1, 2^31 - 1], K outside [1, 64]. */
+int bcos_perturb_select_ws_bytes(int B, int64_t HW, int K, int64_t* bytes);
+
+/* thr_out[b, j] = thr_b(counts[j]) for B images and K removal counts in one call.  scores: device [B, HW]; counts_host: HOST int32 [K],
+ * validated here and handed to the kernels by value in their arguments (as bcos_agc_clip hands over its descriptors); thr_out: device
+ * uint64 [B, K]; ws: device workspace of at least bcos_perturb_select_ws_bytes, owned by the caller -- the call initialises what it
+ * uses of it and never relies on what it held.  Counts may repeat and come in any order.
+ * Method: a radix select on key32 -- four 8-bit passes from the top byte, the prefixes of all K targets resolved together from integer
+ * histograms (LDS atomics per workgroup, integer global atomics between workgroups) -- then one scan per (image, target) over the pixels
+ * in ascending p that takes the r-th pixel whose key32 equals the target's.  Integer counts only: the result is exact, identical from
+ * call to call and independent of the launch shape.  Ten launches (five of them read the scores); nothing is allocated and no device
+ * memory is read by the host.
+ * BCOS_E_INVAL (before anything is launched): a NULL pointer, B / HW / K out of the ranges above, a count outside [0, HW], ws_bytes
+ * too small, thr_out or ws not 8-byte aligned. */
+int bcos_perturb_select(const float* scores, const int32_t* counts_host, int descending, uint64_t* thr_out, void* ws, int64_t ws_bytes,
+                        int B, int64_t HW, int K, void* stream);
+
+/* The prepared network input of copies c in [first, first + n) of the B * K perturbed copies (image-major: c = b * K + j), bit for bit
+ * what bcos_prep_input writes for the materialised copy -- image b with the pixels p of key64_b(p) < thr[b, j] set to 0 in all six
+ * channels -- without the [B * K, 6, H, W] batch ever being stored.  x: [B,6,H,W] NCHW; scores: [B, HW]; thr: device uint64 [B, K]
+ * (bcos_perturb_select with the same `descending`); out: [n,H,W,Cpad], channels >= 6 zero; a removed pixel is (0 - mean) / std in every
+ * channel: the removal acts on the network input BEFORE Normalize.  absmax_out (NULL or [n*H*W]): per-pixel max |out| bit patterns, as
+ * bcos_prep_input.  One thread per output pixel, 16-byte stores for Cpad == 8; source pixel and score are re-read per copy (L2).
+ * 64-bit offsets.
+ * BCOS_E_INVAL: a NULL pointer, B / K / H / W <= 0, Cpad < 6, Cx != 6 or add_inverse != 0 (masking before AddInverse is another
+ * operator), H * W > 2^31 - 1, first < 0, n <= 0 or first + n > B * K, thr not 8-byte aligned. */
+int bcos_prep_input_perturbed(const float* x, const float* scores, const uint64_t* thr, int descending, float* out, const float* mean6,
+                              const float* std6, uint32_t* absmax_out, int B, int K, int first, int n, int Cx, int H, int W, int Cpad,
+                              int add_inverse, void* stream);
+
+/* out[r] = score of class t = targets[r / group] in row r of logits [R, CL]; targets: device int32 [R / group] (R a multiple of group:
+ * the `group` copies of an image share its class).  A target outside [0, CL) yields NaN, never an out-of-bounds read.  With x = the row,
+ * u = 2^-24 and expf accurate to 1 ulp (relative error <= 2u; the device library's expf, not an approximate one) and the division
+ * correctly rounded (relative error <= u) -- both hold for the build bcos_hip/lib.py makes, which passes neither -ffast-math nor
+ * -fno-hip-fp32-correctly-rounded-divide-sqrt; a build with either voids the bounds below:
+ *   mode 0  the logit x_t: an exact copy.
+ *   mode 1  the sigmoid of BcosMixin.to_probabilities: 1 / (1 + expf(-x_t)) -- one expf, one addition, one correctly rounded division:
+ *           |out - sigma(x_t)| <= 6 u sigma(x_t) + 2^-126   (2u + u + u to first order; the absolute term covers an overflowing expf,
+ *           where the result is 0 and sigma(x_t) < 2^-126).
+ *   mode 2  softmax over the row by one wavefront: M = max_c x_c; lane l adds e_c = expf(x_c - M) for c = l, l + 64, ... in ascending
+ *           order as one fp32 chain; the 64 lane sums are combined by the butterfly xor 32, 16, 8, 4, 2, 1; out = expf(x_t - M) / sum.
+ *           With p = softmax(x)_t and D = sum_c softmax(x)_c |x_c - M| (the weighted mean distance to the maximum):
+ *           |out - p| <= (|x_t - M| + D + ceil(CL / 64) + 12) u p + 2^-126
+ *           -- the rounded difference x_c - M perturbs e_c by |x_c - M| u relatively (numerator: |x_t - M| u; sum: D u), each expf adds
+ *           2u to either, a lane's chain and the six butterfly levels add at most ceil(CL / 64) + 5 roundings of a sum of non-negative
+ *           terms, the division one; 12 = 2 + 2 + 5 + 1 and 2 for the second-order terms.  The absolute term covers e_t underflowing.
+ * BCOS_E_INVAL: a NULL pointer, R / CL / group <= 0, R not a multiple of group, mode outside 0..2. */
+int bcos_class_scores(const float* logits, const int32_t* targets, int group, int mode, float* out, int64_t R, int CL, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
