@@ -19,7 +19,7 @@ LIB_PATH = Path(os.environ["BCOS_HIP_LIB"]) if os.environ.get("BCOS_HIP_LIB") el
 CSRC = PKG_ROOT / "csrc"
 INCLUDE = REPO_ROOT / "include"
 SOURCES = ["bcos_tapconv.hip", "bcos_skinny.hip", "bcos_elementwise.hip", "bcos_vit.hip", "bcos_render.hip", "bcos_train.hip",
-           "bcos_agc.hip", "bcos_occlusion.hip", "bcos_perturb.hip", "bcos_head.hip", "bcos_boundary.hip", "bcos_abi.hip"]
+           "bcos_agc.hip", "bcos_occlusion.hip", "bcos_perturb.hip", "bcos_head.hip", "bcos_boundary.hip", "bcos_dense.hip", "bcos_abi.hip"]
 
 BCOS_NONE, BCOS_CONV_EPS, BCOS_LINEAR_EPS = 0, 1, 2
 BCOS_EPI_NORM_ONLY = 1
@@ -192,6 +192,8 @@ SIGNATURES = {
     "bcos_perturb_select": (C.c_int, [_P, _P, _I, _P, _P, _L, _I, _L, _I, _P]),
     "bcos_prep_input_perturbed": (C.c_int, [_P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "bcos_class_scores": (C.c_int, [_P, _P, _I, _I, _P, _L, _I, _P]),
+    "bcos_slice_affine_rows": (C.c_int, [_P, _L, _P, _P, _P, _P, _L, _P, _L, _I, _I, _P]),
+    "bcos_slice_affine_bwd_acc": (C.c_int, [_P, _P, _L, _P, _P, _P, _L, _L, _I, _I, _I, _P]),
 }
 
 _lib = None

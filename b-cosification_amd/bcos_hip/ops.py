@@ -1592,6 +1592,61 @@ def channel_affine_rows(x, scale, shift=None, addend=None, relu=False):
     return out
 
 
+def _row_slice(t: torch.Tensor, what: str):
+    """(rows, C, pitch) of `t` [..., C] read as rows of C floats `pitch` floats apart: a contiguous tensor or the channel slice
+    `X[..., lo:hi]` of one (what the dense-block kernels walk, include/bcos_hip.h: bcos_slice_affine_rows)."""
+    Cc = t.shape[-1]
+    try:
+        t2 = t.view(-1, Cc)           # (fails where the leading dimensions do not collapse to one row stride)
+    except RuntimeError:
+        t2 = None
+    if t2 is None or t2.stride(1) != 1 or (t2.shape[0] > 1 and t2.stride(0) < Cc):
+        raise BcosHipError(f"{what}: expected a contiguous [..., C] tensor or a channel slice of one, got shape {tuple(t.shape)} strides {t.stride()}")
+    rows, pitch = t2.shape[0], (t2.stride(0) if t2.shape[0] > 1 else Cc)
+    return rows, Cc, pitch
+
+
+def slice_affine_rows(x, scale=None, shift=None, mul=None, relu=False, out=None, want_absmax=True):
+    """out = [relu](x * scale[c] + shift[c]) [* mul] over the rows of a channel slice `x` = X[..., lo:hi] (or a dense tensor) into a dense
+    tensor or the slice `out` (include/bcos_hip.h: bcos_slice_affine_rows); every stage is optional.  `want_absmax` attaches the per-row
+    maxima of a dense, newly made `out` (what the split-f16 contraction reading it needs); for a slice `out` they are returned only."""
+    lib = _l.load()
+    rows, Cc, xp = _row_slice(x, "slice_affine_rows.x")
+    fresh = out is None
+    if fresh:
+        out = torch.empty(tuple(x.shape), device=x.device, dtype=torch.float32)
+    orows, oc, yp = _row_slice(out, "slice_affine_rows.out")
+    if (orows, oc) != (rows, Cc):
+        raise BcosHipError(f"slice_affine_rows: out holds {orows} rows of {oc}, x {rows} rows of {Cc}")
+    if mul is not None and (mul.numel() != rows * Cc or not mul.is_contiguous()):
+        raise BcosHipError("slice_affine_rows: mul must be a dense tensor of the slice's shape")
+    am = torch.empty((rows,), device=x.device, dtype=torch.int32) if want_absmax else None      # (written plainly: no zero fill)
+    _l.check(lib.bcos_slice_affine_rows(_dev(x, "x", contiguous=False), xp, _dev(scale, "scale"), _dev(shift, "shift"), _dev(mul, "mul"),
+                                        _dev(out, "y", contiguous=False), yp, C.c_void_p(am.data_ptr()) if am is not None else None,
+                                        rows, Cc, int(bool(relu)), _stream()), "bcos_slice_affine_rows")
+    if am is not None and yp == Cc:
+        _attach_absmax(out, am)
+    return (out, am) if not fresh else out
+
+
+def slice_affine_bwd_acc(d, g, x=None, scale=None, shift=None, relu=False, accumulate=True):
+    """g (+)= d * scale[c] * gate over the rows of the channel slice `g` = G[..., lo:hi], gate = (x * scale + shift > 0) rebuilt from the
+    forward's input slice `x` with the forward kernel's own rounding (include/bcos_hip.h: bcos_slice_affine_bwd_acc).  `d` is dense."""
+    lib = _l.load()
+    rows, Cc, gp = _row_slice(g, "slice_affine_bwd_acc.g")
+    xp = 0
+    if x is not None:
+        xrows, xc, xp = _row_slice(x, "slice_affine_bwd_acc.x")
+        if (xrows, xc) != (rows, Cc):
+            raise BcosHipError(f"slice_affine_bwd_acc: x holds {xrows} rows of {xc}, g {rows} rows of {Cc}")
+    if d.numel() != rows * Cc or not d.is_contiguous():
+        raise BcosHipError("slice_affine_bwd_acc: d must be a dense tensor of the slice's shape")
+    _l.check(lib.bcos_slice_affine_bwd_acc(_dev(d, "d"), _dev(x, "x", contiguous=False), xp, _dev(scale, "scale"), _dev(shift, "shift"),
+                                           _dev(g, "g", contiguous=False), gp, rows, Cc, int(bool(relu)), int(bool(accumulate)), _stream()),
+             "bcos_slice_affine_bwd_acc")
+    return g
+
+
 def relu_bwd(g, act, out=None):
     """out = act > 0 ? g : 0 (include/bcos_hip.h: bcos_relu_bwd)."""
     lib = _l.load()

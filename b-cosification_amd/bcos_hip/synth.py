@@ -61,12 +61,29 @@ def standard_resnet(arch: str, seed: int = 0, resnet_cls=None, blocks=None):
     return net
 
 
+def assign_path(root: nn.Module, path: str, value):
+    """`root.<path> = value` for the attribute / index paths of `standard_changes` ('maxpool', 'features[3]'): what the reference
+    does with exec (bcosification/model.py:47-49), restricted to dotted names and integer indices."""
+    import re
+    steps = re.findall(r"([A-Za-z_]\w*)|\[(\d+)\]", path)
+    if not steps or "".join(f".{n}" if n else f"[{i}]" for n, i in steps).lstrip(".") != path:
+        raise ValueError(f"standard_changes: cannot parse the path {path!r}")
+    obj = root
+    for name, idx in steps[:-1]:
+        obj = getattr(obj, name) if name else obj[int(idx)]
+    name, idx = steps[-1]
+    if name:
+        setattr(obj, name, value)
+    else:
+        obj[int(idx)] = value
+
+
 def finish_conversion(model: nn.Module, model_config: dict, hip_pools: bool = True):
     """bcosification/model.py:44-55: apply `standard_changes`, then null every bias.  `hip_pools` swaps plain
     nn.AvgPool2d modules for the HIP-backed subclass (bcos/modules/pooling.py) -- pass False when the modules
     are the reference's own (golden generation on CPU)."""
     for k, v in (model_config.get("standard_changes") or {}).items():
-        setattr(model.model, k, v)
+        assign_path(model.model, k, v)
     if hip_pools:
         from bcos.modules.pooling import use_hip_pools
         use_hip_pools(model)
@@ -81,6 +98,36 @@ def build_bcosified_resnet(arch: str = "resnet50", seed: int = 0):
     from bcosify import BcosifyNetwork
     cfg = resnet_model_config(arch)
     net = BcosifyNetwork(standard_resnet(arch, seed), cfg, add_channels=True, logit_layer=True)
+    finish_conversion(net, cfg)
+    return net.eval()
+
+
+def densenet_model_config(num_classes: int = 1000) -> dict:
+    """The `model` section of CONFIGS['densenet_121'] (bcosification/experiment_parameters.py:108-129)."""
+    cfg = resnet_model_config("densenet121")
+    cfg.update(last_layer_name="classifier", args=dict(num_classes=num_classes, logit_bias=-math.log(1000 - 1)),
+               standard_changes={"features[3]": nn.AvgPool2d(kernel_size=3, stride=2, padding=1)})
+    return cfg
+
+
+def standard_densenet(growth: int = 32, block_config=(6, 12, 24, 16), init_features: int = 64, bn_size: int = 4,
+                      num_classes: int = 1000, seed: int = 0, densenet_cls=None):
+    """Step 1-2 for a DenseNet.  `densenet_cls` lets the golden generator pass the reference's own DenseNetBcos."""
+    if densenet_cls is None:
+        from bcos.models.standard_models import DenseNetBcos as densenet_cls
+    torch.manual_seed(seed)
+    net = densenet_cls(growth, tuple(block_config), init_features, bn_size=bn_size, num_classes=num_classes)
+    randomize_batchnorm(net, torch.Generator().manual_seed(seed + 1))
+    return net
+
+
+def build_bcosified_densenet(growth: int = 32, block_config=(6, 12, 24, 16), init_features: int = 64, bn_size: int = 4,
+                             num_classes: int = 1000, seed: int = 0):
+    """Steps 1-3 with this package's modules (DenseNet-121 by default; CPU tensors, move with .to('cuda') afterwards)."""
+    from bcosify import BcosifyNetwork
+    cfg = densenet_model_config(num_classes)
+    net = BcosifyNetwork(standard_densenet(growth, block_config, init_features, bn_size, num_classes, seed), cfg,
+                         add_channels=True, logit_layer=True)
     finish_conversion(net, cfg)
     return net.eval()
 

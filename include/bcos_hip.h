@@ -620,6 +620,35 @@ int bcos_relu_bwd(const float* g, const float* act, float* out, int64_t n, void*
 int bcos_channel_affine_rows(const float* x, const float* scale, const float* shift, const float* addend, float* y,
                              uint32_t* y_absmax, int64_t rows, int C, int relu, void* stream);
 
+/* -- densely connected plans (bcos_dense.hip; additive entry points of ABI v12, recognised by symbol presence) ----- */
+/* Pre-activation of a consumer of a concatenated feature buffer: torchvision's _DenseLayer / _Transition / norm5 apply their own
+ * BatchNormUncentered2d (eval: a per-channel affine map, batchnorm_uncentered.py:46-60) and ReLU to cat(features) in front of the
+ * contraction (reference standard_models.py:56-63 runs `features` and a functional ReLU behind norm5).  With the features of a block
+ * stored once, raw, as channel slices of one NHWC buffer, that is a row-wise map from a slice of pitched rows to a dense operand:
+ *     y[r * y_pitch + c] = act(x[r * x_pitch + c] * scale[c] + shift[c]) [* mul[r * C + c]],   r < rows, c < C,
+ * act = max(., 0) for relu = 1, the identity for relu = 0.  scale, shift and mul may each be NULL (the stage is skipped: with all of
+ * them NULL and relu = 0 the call copies a dense tensor into a slice or a slice out of one, bit for bit).  A pitch of 0 means C.
+ * x * scale + shift is two roundings (product, then sum), the arithmetic of bcos_channel_affine_rows: with mul == NULL and
+ * y_pitch in {0, C}, y and y_absmax carry the bits bcos_channel_affine_rows writes for a contiguous copy of the slice.  mul is one
+ * more rounding.  y_absmax[r] (may be NULL) = fp32 bit pattern of max_c |y[r, c]|, written plainly (no atomics, no zero fill needed).
+ * Nothing outside [0, C) of a pitched row is read or written.
+ * BCOS_E_INVAL: NULL x / y, rows <= 0, C <= 0, C % 4 != 0, relu outside {0, 1}, a nonzero pitch < C or not a multiple of 4, a tensor
+ * that is not 16-byte aligned (y_absmax: 4-byte).  BCOS_E_NOSUP: C > 8192 with C / 4 not a divisor of 64. */
+int bcos_slice_affine_rows(const float* x, int64_t x_pitch, const float* scale, const float* shift, const float* mul, float* y,
+                           int64_t y_pitch, uint32_t* y_absmax, int64_t rows, int C, int relu, void* stream);
+
+/* Its input gradient in explanation mode (the norm's variance is a constant, batchnorm_uncentered.py:46-60, so the map is linear up to
+ * the ReLU gate), added into the consumer's slice of the block's gradient buffer:
+ *     g[r * g_pitch + c] = (accumulate ? g[r * g_pitch + c] : 0) + d[r * C + c] * scale[c] * gate,
+ * gate = (x[r * x_pitch + c] * scale[c] + shift[c] > 0) for relu = 1 -- the SAME expression with the same two roundings as
+ * bcos_slice_affine_rows, so gate <=> (the forward's y > 0) bit for bit -- and 1 for relu = 0 (x may then be NULL).  Per element one
+ * product and one sum, in that order: |g - exact| <= 2^-23 (|g_old| + |d scale|).  accumulate = 0 never reads g (it may hold anything,
+ * NaN included): the first consumer handled on the way back covers every channel of its block, so no zero fill is needed.
+ * scale / shift may be NULL as above; d is dense [rows, C].  Nothing outside [0, C) of a pitched row is read or written.
+ * BCOS_E_INVAL: NULL d / g, relu = 1 without x, rows / C / pitches / alignment as above, accumulate outside {0, 1}.  BCOS_E_NOSUP as above. */
+int bcos_slice_affine_bwd_acc(const float* d, const float* x, int64_t x_pitch, const float* scale, const float* shift, float* g,
+                              int64_t g_pitch, int64_t rows, int C, int relu, int accumulate, void* stream);
+
 /* -- training-mode backward (bcos_train.hip) ------------------------------------------ */
 /* Outside explanation mode the dynamic scale is not detached (bcosconv2d.py:176-194), so with lin = conv(x, W) (+ bias),
  * y = s(lin, norm) * lin:   gx = dgrad(gy * dy/dlin, W) + x (.) PatchSum^T(dL/dnorm / norm),   gW = wgrad(gy * dy/dlin, x).
