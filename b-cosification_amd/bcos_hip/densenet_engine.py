@@ -30,10 +30,10 @@ from typing import Dict, List, Optional
 import torch
 import torch.nn as nn
 
-from . import ops, passes
-from .engine import _Conv, _Consumer, _HeadRank1Consumer, _mul_kwargs, _pair
+from . import ops, plan
+from .engine import Conv, head_consumer, mul_kwargs, pool_params
 from .lib import BCOS_CONV_EPS, BcosHipError
-from .passes import _SUBBATCH_STREAMS, _drive
+from .plan import FusedPlan
 
 __all__ = ["DenseNetEngine", "attach", "detach", "PLAN_LOG"]
 
@@ -73,7 +73,7 @@ class _PreNorm:
 
 
 def _conv(conv, bn, name, bn_name=None):
-    """engine._Conv of a layer of the plan's scope: ungrouped, no MaxOut, B = 2 fixed, no bias handling beyond the kernels' own"""
+    """engine.Conv of a layer of the plan's scope: ungrouped, no MaxOut, B = 2 fixed, no bias handling beyond the kernels' own"""
     lin = getattr(conv, "linear", None)
     if lin is None:
         raise BcosHipError(f"densenet engine: `{name}` is a {type(conv).__name__}, not a B-cos convolution")
@@ -83,7 +83,7 @@ def _conv(conv, bn, name, bn_name=None):
         raise BcosHipError(f"densenet engine: `{name}` is a MaxOut layer (max_out = {conv.max_out}); the plan takes max_out = 1")
     if bn is not None and not _is_bnu(bn):
         raise BcosHipError(f"densenet engine: `{bn_name}` is a {type(bn).__name__}; the plan fuses BatchNormUncentered2d only")
-    c = _Conv(conv, bn)
+    c = Conv(conv, bn)
     if c.b != 2.0 or c.force_pow:
         raise BcosHipError(f"densenet engine: `{name}` has B = {c.b}{' (learnable)' if c.force_pow else ''}; the plan takes B = 2 fixed")
     c.name, c.bn_name = name, bn_name
@@ -110,25 +110,22 @@ class _Transition:
         mods = list(tr.children())
         if len(mods) != 4 or not isinstance(mods[1], nn.ReLU) or not isinstance(mods[3], nn.AvgPool2d):
             raise BcosHipError(f"densenet engine: `{name}` is not norm -> ReLU -> conv -> AvgPool2d")
-        pool = mods[3]
-        self.pool = (_pair(pool.kernel_size)[0], _pair(pool.stride)[0], _pair(pool.padding)[0])
-        if pool.ceil_mode or not pool.count_include_pad or pool.divisor_override is not None:
-            raise BcosHipError(f"densenet engine: `{name}`: unsupported AvgPool2d options")
+        self.pool = pool_params(mods[3], f"densenet engine: `{name}`")
         self.pre = _PreNorm(mods[0], f"{name}.0")
         self.conv = _conv(mods[2], None, f"{name}.2")
         if self.conv.k != (1, 1) or self.conv.stride != (1, 1):
             raise BcosHipError(f"densenet engine: `{name}`: the transition convolution must be 1 x 1 / stride 1")
 
 
-class DenseNetEngine:
+class DenseNetEngine(FusedPlan):
     """Launch plan for `BcosifyNetwork(DenseNetBcos(...))` (bcosify.py:22-53 + standard_models.py:56-63)."""
+    who = "densenet engine"
 
     def __init__(self, net):
         m = getattr(net, "model", None)
         feats = getattr(m, "features", None)
         if feats is None or not hasattr(m, "classifier"):
             raise BcosHipError(f"densenet engine: {type(m).__name__} has no `features` / `classifier`: not a torchvision-style DenseNet")
-        self.net = net
         mods = list(feats.named_children())
         if len(mods) < 6 or not isinstance(mods[2][1], nn.ReLU):
             raise BcosHipError("densenet engine: `features` does not start with conv0 / norm0 / relu0 / pool0")
@@ -138,9 +135,7 @@ class DenseNetEngine:
         if not isinstance(pool, nn.AvgPool2d):
             raise BcosHipError("densenet engine: the stem pool must be nn.AvgPool2d (the B-cosification recipe swaps MaxPool for "
                                "AvgPool2d(3, 2, 1): standard_changes = {'features[3]': ...})")
-        if pool.ceil_mode or not pool.count_include_pad or pool.divisor_override is not None:
-            raise BcosHipError("densenet engine: unsupported AvgPool2d options")
-        self.pool = (_pair(pool.kernel_size)[0], _pair(pool.stride)[0], _pair(pool.padding)[0])
+        self.pool = pool_params(pool, "densenet engine")
         self.blocks: List[List[_Layer]] = []
         self.transitions: List[_Transition] = []
         body, (last_name, last) = mods[4:-1], mods[-1]
@@ -174,17 +169,9 @@ class DenseNetEngine:
                 raise BcosHipError(f"densenet engine: `{reader.name}` reads {reader.cin} channels where the block holds {c}")
             if nxt is not None:
                 c = nxt.conv.cout
-        norm = net.bcosifynormalize
-        self._mean, self._std = tuple(norm.mean), tuple(norm.std)
-        self._dev_consts = {}
-        ll = net.logit_layer
-        self.logit_bias = ll.logit_bias if ll is not None else None
-        self.logit_temperature = ll.logit_temperature if ll is not None else None
+        super().__init__(net)
         self.supports_explain = True
         self._train_plan = False                   # (bcos_hip/train_plan.py: no fused training plan; train() + autograd runs per layer)
-        self._absmax_arena = ops.AbsmaxArena()
-        self.subbatch_streams = _SUBBATCH_STREAMS
-        self._side = passes.SideStreams()
 
     # ------------------------------------------------------------------------------------------------
     def _parts(self):
@@ -208,24 +195,6 @@ class DenseNetEngine:
             if p.fingerprint() != p._fp:
                 p.refresh()
 
-    def _consts(self, device):
-        key = str(device)
-        if key not in self._dev_consts:
-            self._dev_consts[key] = (torch.tensor(self._mean, dtype=torch.float32, device=device),
-                                     torch.tensor(self._std, dtype=torch.float32, device=device))
-            ops.publish_cached(self._dev_consts[key][1])
-        return self._dev_consts[key]
-
-    def _prepare(self, device):
-        self._ensure_fresh()
-        self._consts(device)
-
-    def _passes(self, x, n, make_gen):
-        return self._side.run(x.device, n, self.subbatch_streams, make_gen, self._absmax_arena, lambda: self._prepare(x.device))
-
-    def n_streams(self, x) -> int:
-        return passes.n_streams(x.shape[0], self.subbatch_streams, x.device)
-
     def n_logits(self) -> int:
         return self.head.cout
 
@@ -234,21 +203,15 @@ class DenseNetEngine:
         """norm + ReLU of a channel slice of a block buffer -> the dense operand of the contraction behind it, with its row maxima"""
         return ops.slice_affine_rows(x_slice, pre.scale, pre.shift, relu=True)
 
-    def _run_forward_gen(self, x: torch.Tensor, keep: bool):
-        """The forward pass as a generator (yields behind the stem and behind every dense layer / transition, so that the passes of
-        several sub-batches are issued interleaved); -> (logits, kept state)."""
-        if x.dim() != 4 or x.shape[1] not in (3, 6):
-            raise ValueError(f"expected [N,6,H,W] (or [N,3,H,W] to be AddInverse-encoded), got {tuple(x.shape)}")
-        ops.require_device(x, "bcos_hip.densenet_engine")
-        self._ensure_fresh()
-        x = passes.detached(x)
-        mean, std = self._consts(x.device)
-        add_inverse = x.shape[1] == 3
-        N = x.shape[0]
-        xn = ops.prep_input(x, mean, std, cpad=8, add_inverse=add_inverse, want_absmax=True)
+    def _run_forward_gen(self, src, keep: bool, gates=None):
+        """The forward pass over the images `src` (plan.Images) as a generator (yields behind the stem and behind every dense layer /
+        transition, so that the passes of several sub-batches are issued interleaved); -> (logits, kept state)."""
+        self._refuse(gates=gates)
+        x, xn = self._begin(src)
+        N = src.n
         a, t0 = self.stem.fwd(xn, relu=True, want_scale=keep, track=False)          # (feeds a pool)
         _log(self.stem, None, xn.shape, a.shape)
-        st = dict(x=x, add_inverse=add_inverse, H=x.shape[2], W=x.shape[3], t0=t0, a0_hw=(a.shape[1], a.shape[2]), blocks=[], trans=[]) if keep else None
+        st = dict(x=x, add_inverse=src.add_inverse, H=x.shape[2], W=x.shape[3], t0=t0, a0_hw=(a.shape[1], a.shape[2]), blocks=[], trans=[]) if keep else None
         k, s, p = self.pool
         cur = ops.avgpool2d_fwd(a, k, s, p, want_absmax=False)
         del a, xn
@@ -308,17 +271,13 @@ class DenseNetEngine:
     def _head_gradient(self, st, cls, H, W):
         """d logit[cls] / d (classifier input) [N, H, W, C]: rank one per image through the 1 x 1 classifier (bcos_head_rank1_grad_ex with
         mul = NULL), or the one-hot gradient and the classifier's input-gradient contraction where that launch does not apply"""
-        hc = self.head
-        if hc.stride == (1, 1) and hc.padding == (0, 0) and hc.w_fwd.shape[-1] % 4 == 0 and hc.w_fwd.shape[-1] == hc.cin:
-            consumer = _HeadRank1Consumer(cls, st["tf"], hc.w_fwd.view(hc.w_fwd.shape[0], -1), self.logit_temperature)
-        else:
-            consumer = _Consumer(hc, ops.ensure_absmax(ops.head_onehot_grad(cls, st["tf"], self.logit_temperature)), None, None, 0)
-        d, _ = consumer.run(H, W, t_main=None, td=None, gated=False, track=False)
+        d, _ = head_consumer(self.head, st["tf"], cls, None, self.logit_temperature).run(H, W, t_main=None, td=None, gated=False, track=False)
         return d
 
-    def _backward_gen(self, x, st, cls, want_weights: bool, consume: bool, outs=None):
+    def _backward_gen(self, x, st, cls, want_weights: bool, consume: bool, outs=None, functional=None, g_head=None):
         """Input-gradient pass of logit[cls[n]] for every image n over the state `st` of a kept forward; `consume` frees each kept
         tensor as soon as it has been used (last / only pass over this state)."""
+        self._refuse(functional=functional, cotangent=g_head)
         N = x.shape[0]
         nb = len(self.blocks)
         d, d_pre = None, self.norm5
@@ -339,7 +298,7 @@ class DenseNetEngine:
                 ly = blk[li]
                 c -= ly.growth
                 a = ops.slice_affine_rows(G[..., c:c + ly.growth], mul=rec["s2"][li])     # (its row maxima attached; the 3 x 3 launch derives its per-image range)
-                gl = ly.conv2.dgrad.run(a, H, W, track_absmax=ly.conv1.k_dgrad >= ops.F16X2_MIN_K, **_mul_kwargs(rec["t1"][li]))
+                gl = ly.conv2.dgrad.run(a, H, W, track_absmax=ly.conv1.k_dgrad >= ops.F16X2_MIN_K, **mul_kwargs(rec["t1"][li]))
                 del a
                 dl = ly.conv1.dgrad.run(gl, H, W, track_absmax=False)
                 del gl
@@ -387,12 +346,7 @@ class DenseNetEngine:
     @torch.no_grad()
     def forward(self, x: torch.Tensor, occlude=None, perturb=None) -> torch.Tensor:
         self._refuse(occlude=occlude, perturb=perturb)
-        x = passes.detached(x)
-
-        def one(lo, hi):
-            return (yield from self._run_forward_gen(x[lo:hi], keep=False))[0]
-        parts = self._passes(x, x.shape[0], one)
-        return parts[0] if len(parts) == 1 else torch.cat(parts)
+        return super().forward(x)
 
     @torch.no_grad()
     def explain(self, x: torch.Tensor, targets: Optional[torch.Tensor] = None, want_weights: bool = True, gates=None, cotangent=None,
@@ -400,48 +354,14 @@ class DenseNetEngine:
         """Forward in explanation mode + input-gradient pass of the explained logit of every image (batched bcos/common.py:163-181).
         `targets` [N] int64 selects the logits (default: arg-max)."""
         self._refuse(occlude=occlude, perturb=perturb, functional=functional, gates=gates, cotangent=cotangent)
-        if targets is not None:
-            targets = ops.check_targets(targets, self.head.cout)
-        x = passes.detached(x)
-        outs = None
-        if self.n_streams(x) > 1:
-            outs = passes.explanation_outputs(x, want_weights)
-            targets = None if targets is None else targets.to(device=x.device, dtype=torch.int64).contiguous()
+        return super().explain(x, targets, want_weights)
 
-        def one(lo, hi):
-            xs = x[lo:hi]
-            logits, st = yield from self._run_forward_gen(xs, keep=True)
-            pred, _ = ops.argmax_rows(logits)
-            cls = pred if targets is None else targets[lo:hi].to(device=logits.device, dtype=torch.int64).contiguous()
-            wts, contrib = yield from self._backward_gen(xs, st, cls, want_weights, consume=True,
-                                                         outs=None if outs is None else (None if outs[0] is None else outs[0][lo:hi], outs[1][lo:hi]))
-            return dict(logits=logits, prediction=pred, explained_class_idx=cls, dynamic_linear_weights=wts, contribution_map=contrib)
-        return passes.assemble_explanation(self._passes(x, x.shape[0], one), outs)
-
-    @torch.no_grad()
-    def explain_targets(self, x: torch.Tensor, targets: torch.Tensor, want_weights: bool = False) -> Dict[str, torch.Tensor]:
-        """ONE forward in explanation mode, then one input-gradient pass per target column: `targets` [N, T] (or [T], shared by all
-        images).  Returns logits [N, K], contribution_maps [N, T, H, W] and, if requested, dynamic_linear_weights [N, T, 6, H, W]."""
-        targets = ops.check_targets(targets, self.head.cout)
-        x = passes.detached(x)
-
-        def columns(logits):
-            tg = targets.to(device=logits.device, dtype=torch.int64)
-            return (tg.view(1, -1).expand(x.shape[0], -1) if tg.dim() == 1 else tg).unbind(1)
-        with ops.absmax_arena(self._absmax_arena, x.device):
-            return passes.explain_repeated(x, lambda: _drive(self._run_forward_gen(x, keep=True)), columns,
-                                           lambda st, cls, last: _drive(self._backward_gen(x, st, cls.contiguous(), want_weights, consume=last)),
-                                           want_weights)
+    explain_targets = FusedPlan._explain_targets
 
 
 def attach(net) -> DenseNetEngine:
-    """Compile `net` (a BcosifyNetwork around a torchvision-style DenseNetBcos) and make `net(x)` (under no_grad, eval mode) and
-    `net.explain_batch(x)` use the fused plan.  Raises BcosHipError, with the reason, for a network outside the plan's scope."""
-    eng = DenseNetEngine(net)
-    object.__setattr__(net, "_bcos_engine", eng)
-    return eng
+    """Compile `net` (a BcosifyNetwork around a torchvision-style DenseNetBcos) into the fused plan (bcos_hip/plan.py: attach)."""
+    return plan.attach(net, DenseNetEngine)
 
 
-def detach(net):
-    if hasattr(net, "_bcos_engine"):
-        object.__delattr__(net, "_bcos_engine")
+detach = plan.detach

@@ -23,11 +23,11 @@ from typing import Dict, List, Optional
 import torch
 import torch.nn as nn
 
-from . import ops, passes
-from .functional import LogitFunctional, as_functional
+from . import ops, plan
 from .lib import (BCOS_CONV_EPS, BCOS_EPI_FORCE_POW, BCOS_EPI_GATE2_FROM_MUL, BCOS_EPI_MUL_FROM_ACT, BCOS_EPI_SCALE_GATE_LSB,
                   BCOS_E_NOSUP, BCOS_NONE, BcosHipError)
-from .passes import _SUBBATCH_MIN, _SUBBATCH_STREAMS, _drive      # noqa: F401  (the sub-batch defaults: bcos_hip/passes.py)
+from .passes import _SUBBATCH_MIN      # noqa: F401  (the sub-batch default: bcos_hip/passes.py)
+from .plan import FusedPlan
 
 _GATE_TENSOR = bool(os.environ.get("BCOS_GATE_TENSOR"))   # development switch: ReLU gates as tensors, not as the bit in t
 # The multiplier t of conv1 / conv2 of every block (B = 2, own ReLU, no residual) is REBUILT from the kept activation, the patch
@@ -59,64 +59,11 @@ def set_boundary_fusion(on):
     return old
 
 
-def check_occluded_input(x, rects):
-    """forward(x, occlude=rects) of both engines: one contiguous 6-channel device image and a device bank [n, 4]; -> (x, n)"""
-    if x.dim() != 4 or x.shape[0] != 1 or x.shape[1] != 6:
-        raise ValueError(f"forward(x, occlude=...): expected ONE 6-channel image [1,6,H,W] (the masks multiply the network input; "
-                         f"masking before AddInverse is a different operator), got {tuple(x.shape)}")
-    ops.require_device(x, "bcos_hip.engine")
-    if not (torch.is_tensor(rects) and rects.device == x.device and rects.dtype == torch.int32 and rects.dim() == 2      # (x is on a device)
-            and rects.shape[1] == 4 and rects.is_contiguous() and rects.shape[0] > 0):
-        raise ValueError("forward(x, occlude=...): the mask bank is a contiguous int32 tensor [n, 4] of rectangles on the image's device")
-    return passes.detached(x), rects.shape[0]
-
-
-def check_perturbed_input(x, plan):
-    """forward(x, perturb=plan) of both engines: contiguous 6-channel device images [B,6,H,W] and a plan (bcos_hip.perturbation.PerturbPlan:
-    scores [B, H*W], thr [B, K], descending, K) on their device; -> (x, B * K)"""
-    if x.dim() != 4 or x.shape[1] != 6:
-        raise ValueError(f"forward(x, perturb=...): expected 6-channel images [B,6,H,W] (pixels are removed from the network input; "
-                         f"masking before AddInverse is a different operator), got {tuple(x.shape)}")
-    ops.require_device(x, "bcos_hip.engine")
-    B, _, H, W = x.shape
-    scores, thr, K = getattr(plan, "scores", None), getattr(plan, "thr", None), getattr(plan, "K", None)
-    if not (torch.is_tensor(scores) and scores.device == x.device and scores.dtype == torch.float32 and tuple(scores.shape) == (B, H * W)
-            and scores.is_contiguous() and torch.is_tensor(thr) and thr.device == x.device and thr.dtype == torch.int64
-            and isinstance(K, int) and K > 0 and tuple(thr.shape) == (B, K) and thr.is_contiguous() and hasattr(plan, "descending")):
-        raise ValueError("forward(x, perturb=...): the plan holds contiguous scores [B, H*W] (float32) and thr [B, K] (int64, from "
-                         "ops.perturb_select) on the images' device, `descending` and K")
-    return passes.detached(x), B * K
-
-
-def forward_passes(eng, x, occlude=None, perturb=None):
-    """forward(x, occlude=... / perturb=...) of both engines from the engine's forward generator: the head output of the batch x, of the n
-    occluded copies of the ONE image x, or of the B * K perturbed copies of the images x (cut where forward() cuts an n-image batch)"""
-    if occlude is not None and perturb is not None:
-        raise ValueError("forward(x, occlude=..., perturb=...): one of the two at a time")
-    if perturb is not None:
-        x, n = check_perturbed_input(x, perturb)
-    elif occlude is None:
-        x = passes.detached(x)
-        n = x.shape[0]
-    else:
-        x, n = check_occluded_input(x, occlude)
-
-    def one(lo, hi):
-        if perturb is not None:
-            gen = eng._run_forward_gen(x, keep=False, perturb=(perturb, lo, hi - lo))
-        else:
-            gen = (eng._run_forward_gen(x[lo:hi], keep=False) if occlude is None
-                   else eng._run_forward_gen(x, keep=False, occlude=(occlude, lo, hi - lo)))
-        return (yield from gen)[0]
-    parts = eng._passes(x, n, one)
-    return parts[0] if len(parts) == 1 else torch.cat(parts)
-
-
 def _pair(v):
     return (v, v) if isinstance(v, int) else (int(v[0]), int(v[1]))
 
 
-class _Conv:
+class Conv:
     """Kernel-side view of one BcosifyConv2d (+ the BatchNormUncentered2d that follows it)."""
 
     def __init__(self, conv, bn, cin_pad_to=4, main_path=False):
@@ -306,7 +253,7 @@ class _ActScale:
         return dict(mul=self.act, mul_norm=self.norm, mul_csc=self.ch_scale, mul_csh=self.ch_shift, flags=BCOS_EPI_MUL_FROM_ACT)
 
 
-def _mul_kwargs(t):
+def mul_kwargs(t):
     """epilogue arguments that multiply a gradient by the layer multiplier `t` (stored tensor or _ActScale record)"""
     return t.kwargs() if isinstance(t, _ActScale) else dict(mul=t)
 
@@ -319,7 +266,7 @@ class _Block:
     def __init__(self, block):
         names = [n for n in ("conv1", "conv2", "conv3") if hasattr(block, n)]
         # Grouped convolutions (ResNeXt-style `groups`, bcosconv2d.py:84-140) and MaxOut ones (:166-170, 2 or 4 filters per unit) on the
-        # main path are fused nodes like any other since round 4 (_Conv.groups, _Conv._fwd_maxout).  What the fused launches do not
+        # main path are fused nodes like any other since round 4 (Conv.groups, Conv._fwd_maxout).  What the fused launches do not
         # take -- group widths that are not multiples of four, other unit sizes, grouped MaxOut, a MaxOut shortcut -- makes the block a
         # HYBRID node: it runs layer by layer on the nn.Module path (one fused HIP launch per layer: bcos/modules/_hipfn.py) and its input
         # gradient comes from that path's own backward; the blocks around it stay fused.
@@ -336,7 +283,7 @@ class _Block:
         if self.hybrid:
             self.convs, self.shortcut, self.pool, self.shortcut_pool, self.relu = [], None, 0, 0, True
             return
-        self.convs = [_Conv(getattr(block, n), getattr(block, n.replace("conv", "bn")), main_path=True) for n in names]
+        self.convs = [Conv(getattr(block, n), getattr(block, n.replace("conv", "bn")), main_path=True) for n in names]
         self.k_first = self.convs[0].k_fwd
         relus = [getattr(block, r) for r in ("relu", "relu1", "relu2", "relu3") if hasattr(block, r)]
         self.relu = all(isinstance(r, nn.ReLU) for r in relus)
@@ -356,7 +303,7 @@ class _Block:
                 mods = mods[1:]
             if len(mods) != 2:
                 raise BcosHipError("engine: downsample must be ([AvgPool2d,] conv, norm)")
-            self.shortcut = _Conv(mods[0], mods[1])
+            self.shortcut = Conv(mods[0], mods[1])
 
     def refresh(self):
         for c in self.convs:
@@ -374,18 +321,28 @@ def _pool_stride(pool: nn.AvgPool2d) -> int:
     return 0 if k[0] == 1 else k[0]
 
 
-class ResNetEngine:
+def pool_params(pool: nn.AvgPool2d, who: str):
+    """(kernel, stride, padding) of a stem / transition AvgPool2d, of the options the pooling launches take"""
+    if pool.ceil_mode or not pool.count_include_pad or pool.divisor_override is not None:
+        raise BcosHipError(f"{who}: unsupported AvgPool2d options")
+    return _pair(pool.kernel_size)[0], _pair(pool.stride)[0], _pair(pool.padding)[0]
+
+
+_NO_CLASS_LOGITS = ("engine: an attn_unpool head has no class logits of its own: pass `cotangent` "
+                    "(bcos_hip.clip_head.zeroshot_attribution builds it from the text embeddings)")
+
+
+class ResNetEngine(FusedPlan):
     """Launch plan for `BcosifyNetwork(ResNetBcos(...))` (bcosify.py:22-53 + standard_models.py:36-54)."""
 
     def __init__(self, net):
         m = net.model
-        self.net = net
         for attr in ("conv1", "bn1", "layer1", "layer2", "layer3", "layer4"):
             if not hasattr(m, attr):
                 raise BcosHipError(f"engine: {type(m).__name__} has no `{attr}`: not a ResNet-style network")
         if hasattr(m, "attnpool"):
             # CLIP ModifiedResNet (CLIP/clip/model.py:94-154): 3-conv stem + AvgPool2d(2), attention-pool head
-            self.stem = [(_Conv(getattr(m, f"conv{i}"), getattr(m, f"bn{i}")), isinstance(getattr(m, f"relu{i}"), nn.ReLU))
+            self.stem = [(Conv(getattr(m, f"conv{i}"), getattr(m, f"bn{i}")), isinstance(getattr(m, f"relu{i}"), nn.ReLU))
                          for i in (1, 2, 3)]
             pool = m.avgpool
             # pooled head, or the `attn_unpool` variant that projects every location and L2-normalises it (bcosattnpool.py:23-32)
@@ -396,32 +353,22 @@ class ResNetEngine:
             for attr in ("relu", "maxpool", "fc", "avgpool"):
                 if not hasattr(m, attr):
                     raise BcosHipError(f"engine: {type(m).__name__} has no `{attr}`: not a torchvision-style ResNet")
-            self.stem = [(_Conv(m.conv1, m.bn1), isinstance(m.relu, nn.ReLU))]
+            self.stem = [(Conv(m.conv1, m.bn1), isinstance(m.relu, nn.ReLU))]
             pool = m.maxpool
             self.head_kind = "gap_fc"
-            self.head = _Conv(m.fc, None)
+            self.head = Conv(m.fc, None)
         if not isinstance(pool, nn.AvgPool2d):
             raise BcosHipError("engine: the stem pool must be nn.AvgPool2d (the B-cosification recipe swaps MaxPool for "
                                "AvgPool2d(3,2,1): bcosification/experiment_parameters.py:99)")
-        self.pool = (_pair(pool.kernel_size)[0], _pair(pool.stride)[0], _pair(pool.padding)[0])
-        if pool.ceil_mode or not pool.count_include_pad or pool.divisor_override is not None:
-            raise BcosHipError("engine: unsupported AvgPool2d options")
+        self.pool = pool_params(pool, "engine")
         self.blocks: List[_Block] = []
         for li in range(1, 5):
             for blk in getattr(m, f"layer{li}").children():
                 self.blocks.append(_Block(blk))
-        norm = net.bcosifynormalize
-        self._mean, self._std = tuple(norm.mean), tuple(norm.std)
-        self._dev_consts = {}
-        ll = net.logit_layer
-        self.logit_bias = ll.logit_bias if ll is not None else None
-        self.logit_temperature = ll.logit_temperature if ll is not None else None
+        # (two sub-batch streams; three, measured on the CLIP image encoder at batch 256: 8 650 / 8 705 against 8 651 / 8 608 images/s
+        #  with two, same node -- within the noise; the ViT plan, whose launches are shorter still, does gain: bcos_hip/vit_engine.py)
+        super().__init__(net)
         self.supports_explain = True
-        self._absmax_arena = ops.AbsmaxArena()      # per-pixel operand maxima of one pass (f16x2 contraction)
-        self.subbatch_streams = _SUBBATCH_STREAMS   # 1 = every pass on the caller's stream
-        # (three streams, measured on the CLIP image encoder at batch 256: 8 650 / 8 705 against 8 651 / 8 608 images/s with two, same
-        #  node -- within the noise; the ViT plan, whose launches are shorter still, does gain: bcos_hip/vit_engine.py)
-        self._side = passes.SideStreams()           # (streams, arenas) of the sub-batch passes, created on first use
         if self.head_kind in ("attnpool", "attn_unpool"):
             self._refresh_attnpool()
 
@@ -494,42 +441,16 @@ class ResNetEngine:
         if self.head_kind in ("attnpool", "attn_unpool") and self._attnpool_fingerprint() != getattr(self, "_ap_fp", None):
             self._refresh_attnpool()
 
-    def _consts(self, device):
-        key = str(device)
-        if key not in self._dev_consts:
-            self._dev_consts[key] = (torch.tensor(self._mean, dtype=torch.float32, device=device),
-                                     torch.tensor(self._std, dtype=torch.float32, device=device))
-            ops.publish_cached(self._dev_consts[key][1])
-        return self._dev_consts[key]
-
     # ------------------------------------------------------------------------------------------------
-    def _run_forward(self, x: torch.Tensor, keep: bool, gates=None):
-        return _drive(self._run_forward_gen(x, keep, gates))
-
-    def _run_forward_gen(self, x: torch.Tensor, keep: bool, gates=None, occlude=None, perturb=None):
-        """The forward pass as a generator: it yields (nothing) behind the stem and behind every block, so that the passes of several
-        sub-batches can be ISSUED interleaved (see _interleave); its return value is (head output, kept state).
-        `occlude` = (bank, first, n): the batch is the n copies of the ONE image x occluded by bank[first:first + n] (forward only).
-        `perturb` = (plan, first, n): the batch is copies [first, first + n) of the perturbed copies of the images x (forward only)."""
-        if x.dim() != 4 or x.shape[1] not in (3, 6):
-            raise ValueError(f"expected [N,6,H,W] (or [N,3,H,W] to be AddInverse-encoded), got {tuple(x.shape)}")
-        ops.require_device(x, "bcos_hip.engine")
-        self._ensure_fresh()
-        x = x.detach()
-        x = x if x.is_contiguous() else x.contiguous()
-        mean, std = self._consts(x.device)
-        add_inverse = x.shape[1] == 3
-        if perturb is not None:
-            xn = ops.prep_input_perturbed(x, perturb[0].scores, perturb[0].thr, mean, std, descending=perturb[0].descending,
-                                          first=perturb[1], n=perturb[2], cpad=8, want_absmax=True)
-        elif occlude is None:
-            xn = ops.prep_input(x, mean, std, cpad=8, add_inverse=add_inverse, want_absmax=True)
-        else:
-            xn = ops.prep_input_occluded(x, occlude[0], mean, std, first=occlude[1], n=occlude[2], cpad=8, want_absmax=True)
+    def _run_forward_gen(self, src, keep: bool, gates=None):
+        """The forward pass over an input source (bcos_hip/plan.py) as a generator: it yields (nothing) behind the stem and behind every
+        block, so that the passes of several sub-batches can be ISSUED interleaved (see _interleave); its return value is (head output,
+        kept state)."""
+        x, xn = self._begin(src)
         gates = list(gates) if gates is not None else None
         if gates is not None and any(b.hybrid for b in self.blocks):
             raise BcosHipError("engine: replayed ReLU gates are not available for networks with a block on the nn.Module path (hybrid node)")
-        st = dict(x=x, add_inverse=add_inverse, H=x.shape[2], W=x.shape[3], stem_ts=[], stem_hws=[], blocks=[]) if keep else None
+        st = dict(x=x, add_inverse=src.add_inverse, H=x.shape[2], W=x.shape[3], stem_ts=[], stem_hws=[], blocks=[]) if keep else None
         a = xn
         need = lambda k: k >= ops.F16X2_MIN_K      # noqa: E731  will the reader of a tensor use its per-pixel maxima?
         for si, (conv, relu) in enumerate(self.stem):
@@ -714,154 +635,39 @@ class ResNetEngine:
         g_lin = g_v[:, 1:] + g_v[:, :1] / float(H * W)                   # positions + their share of the mean token
         return ops.ensure_absmax(g_lin.reshape(N, H, W, C).contiguous())
 
-    def _prepare(self, device):
-        """everything the passes cache lazily, brought up to date on the current stream (passes.SideStreams.run)"""
-        self._ensure_fresh()
-        self._consts(device)
-
     def _stream_limit(self, cotangent=None) -> int:
+        """ONE stream for a `cotangent` callable (it is handed the head output of the whole batch at once) and for the `attn_unpool`
+        head (its output is token-major)"""
         return 1 if (cotangent is not None or self.head_kind == "attn_unpool") else self.subbatch_streams
-
-    def _passes(self, x, n, make_gen, cotangent=None):
-        return self._side.run(x.device, n, self._stream_limit(cotangent), make_gen, self._absmax_arena, lambda: self._prepare(x.device))
-
-    @torch.no_grad()
-    def forward(self, x: torch.Tensor, occlude: Optional[torch.Tensor] = None, perturb=None) -> torch.Tensor:
-        """`occlude` (a device bank [n, 4] of int32 rectangles, include/bcos_hip.h): x is ONE 6-channel image [1, 6, H, W] and the result
-        the head output [n, ...] of its n occluded copies `x * mask_i` (occlusion.py:80-90) -- the copies are never built: the prepared
-        input comes from ops.prep_input_occluded, everything behind it is the plan of an n-image batch, sub-batch streams included.
-        `perturb` (bcos_hip.perturbation.PerturbPlan: scores [B, H*W], thr [B, K], descending, K): x is [B, 6, H, W] and the result the
-        head output [B * K, ...], image-major, of the copies with the first k_j pixels of every image's ranking removed -- prepared by
-        ops.prep_input_perturbed, then the plan of a B * K-image batch, cut along the copy index.  Not together with `occlude`."""
-        return forward_passes(self, x, occlude, perturb)
-
-    @torch.no_grad()
-    def explain(self, x: torch.Tensor, targets: Optional[torch.Tensor] = None, want_weights: bool = True,
-                gates=None, cotangent=None, functional: Optional[LogitFunctional] = None) -> Dict[str, torch.Tensor]:
-        """Forward in explanation mode + input-gradient pass of the explained logit of every image
-        (batched bcos/common.py:163-181).  `targets` [N] int64 selects the logits (default: arg-max).
-        `gates`: optional list of NHWC 0/1 tensors, one per ReLU in execution order, that REPLACE the v > 0
-        decisions (replay of gates recorded elsewhere; used by the gate-pinned parity test).
-        `cotangent` (attention-pool heads): a callable that receives the head output -- the embeddings [N, D], or [(HW), N, D']
-        for an `attn_unpool` head -- and returns d(scalar to explain) / d(head output) of the same shape; the input-gradient
-        pass then starts from it instead of from a one-hot coordinate (the zero-shot text logit of
-        interpretability/analyses/text_localisation.py:68-126: bcos_hip.clip_head.zeroshot_attribution).
-        `functional` (bcos_hip.functional.LogitFunctional, instead of `targets`): explain a linear functional sum_k c_k y_k of the logits --
-        a contrast y_a - y_b, the mean-corrected y_t - mean_k y_k -- at the cost of one ordinary pass (the network is linear in the head
-        cotangent); the result carries `functional_value` [N] (sum_k c_k logit_k) in place of `explained_class_idx`."""
-        functional = self._checked_functional(x, functional, targets, cotangent)
-        if targets is not None and self.head_kind == "gap_fc":
-            targets = ops.check_targets(targets, self.head.cout)       # IndexError like the reference's out[0, idx]; negative indices wrap
-        x = passes.detached(x)
-        outs = None
-        if self.n_streams(x, cotangent=cotangent) > 1:
-            # sub-batches write into ONE set of output tensors and read ONE device copy of the targets; a single pass allocates its
-            # outputs and moves its targets behind its forward, as it always did
-            outs = passes.explanation_outputs(x, want_weights)
-            targets = None if targets is None else targets.to(device=x.device, dtype=torch.int64).contiguous()
-
-        def one(lo, hi):
-            cut = lambda t: None if t is None else t[lo:hi]      # noqa: E731
-            return self._explain_one_gen(x[lo:hi], cut(targets), want_weights,
-                                         None if gates is None else [gt[lo:hi] for gt in gates],       # (replayed ReLU decisions: [N, ...] like the activations)
-                                         cotangent, outs=None if outs is None else (cut(outs[0]), outs[1][lo:hi]),
-                                         functional=None if functional is None else functional[lo:hi].to(x.device))
-        return passes.assemble_explanation(self._passes(x, x.shape[0], one, cotangent), outs)
 
     def n_logits(self) -> int:
         """width of the head output a target index / a functional's cotangent refers to (attention-pool heads: the embedding)"""
         return self.head.cout if self.head_kind == "gap_fc" else self.ap_w["c"].shape[0]
 
+    def _check_targets(self, targets, logits=None):
+        """gap_fc heads: on the host before any launch; attention-pool heads: against the embedding width, behind the forward"""
+        if logits is not None and self.head_kind == "attn_unpool":
+            raise BcosHipError(_NO_CLASS_LOGITS)
+        if (logits is None) == (self.head_kind == "gap_fc"):
+            return ops.check_targets(targets, self.head.cout if logits is None else logits.shape[1])
+        return targets
+
     def _checked_functional(self, x, functional, targets=None, cotangent=None):
-        """a `functional` argument validated on the host before any launch and moved to x's device (None stays None)"""
-        functional = as_functional(functional)
-        if functional is None:
-            return None
-        if targets is not None or cotangent is not None:
-            raise ValueError("engine: `functional` replaces `targets` / `cotangent`: pass one of them")
-        if self.head_kind == "attn_unpool":
-            raise BcosHipError("engine: an attn_unpool head has no class logits of its own: pass `cotangent` "
-                               "(bcos_hip.clip_head.zeroshot_attribution builds it from the text embeddings)")
-        return functional.checked(x.shape[0], self.n_logits()).to(x.device)
+        if functional is not None and self.head_kind == "attn_unpool":
+            raise BcosHipError(_NO_CLASS_LOGITS)
+        return super()._checked_functional(x, functional, targets, cotangent)
 
-    def n_streams(self, x, cotangent=None) -> int:
-        """On how many sub-batch streams does explain(x, ...) run?  `subbatch_streams` (default 2) for a batch of at least that many
-        times _SUBBATCH_MIN images on a device -- replayed `gates` included: they are cut along the batch like the images -- and ONE
-        in exactly three cases: a `cotangent` callable (it is handed the head output of the whole batch at once), the `attn_unpool`
-        head (its output is token-major), and a pass that is being captured into a hipGraph.  Results
-        do not depend on the answer: an image's bits are a function of the image alone."""
-        return passes.n_streams(x.shape[0], self._stream_limit(cotangent), x.device)
+    explain_targets = FusedPlan._explain_targets
+    explain_functionals = FusedPlan._explain_functionals
 
-    def _explain_one_gen(self, x, targets, want_weights, gates, cotangent, outs=None, functional=None):
-        """forward + input-gradient pass of one (sub-)batch as a generator (yields behind every block of either pass); the caller owns
-        the stream and the maxima arena the launches are issued under"""
-        logits, st = yield from self._run_forward_gen(x, keep=True, gates=gates)
-        if cotangent is not None:
-            if self.head_kind not in ("attnpool", "attn_unpool"):
-                raise BcosHipError("engine: `cotangent` needs an attention-pool head (CLIP image encoder)")
-            g_head = cotangent(logits)
-            if tuple(g_head.shape) != tuple(logits.shape):
-                raise ValueError(f"cotangent: expected shape {tuple(logits.shape)}, got {tuple(g_head.shape)}")
-            wts, contrib = yield from self._backward_gen(x, st, None, want_weights, consume=True, g_head=g_head, outs=outs)
-            return dict(logits=logits, embedding=logits, dynamic_linear_weights=wts, contribution_map=contrib)
-        if self.head_kind == "attn_unpool":
-            raise BcosHipError("engine: an attn_unpool head has no class logits of its own: pass `cotangent` "
-                               "(bcos_hip.clip_head.zeroshot_attribution builds it from the text embeddings)")
-        pred, _ = ops.argmax_rows(logits)
-        if functional is not None:
-            wts, contrib = yield from self._backward_gen(x, st, None, want_weights, consume=True, outs=outs, functional=functional)
-            return dict(logits=logits, prediction=pred, functional_value=functional.value(logits), dynamic_linear_weights=wts,
-                        contribution_map=contrib)
-        if targets is not None and self.head_kind != "gap_fc":
-            targets = ops.check_targets(targets, logits.shape[1])      # (attention-pool head: the embedding width; gap_fc heads were checked in explain())
-        cls = pred if targets is None else targets.to(device=logits.device, dtype=torch.int64).contiguous()
-        wts, contrib = yield from self._backward_gen(x, st, cls, want_weights, consume=True, outs=outs)
-        return dict(logits=logits, prediction=pred, explained_class_idx=cls, dynamic_linear_weights=wts,
-                    contribution_map=contrib)
-
-    @torch.no_grad()
-    def explain_targets(self, x: torch.Tensor, targets: torch.Tensor, want_weights: bool = False) -> Dict[str, torch.Tensor]:
-        """ONE forward in explanation mode, then one input-gradient pass per target column: `targets` [N, T] (or [T],
-        shared by all images).  The reference's `attribute_selection` (interpretability/explanation_methods/utils.py:84-99,
-        bcos/common.py:319-344) re-runs the forward for every target; the dynamic weights of the forward do not depend on
-        the explained logit, so they are kept and only the backward is repeated.
-        Returns logits [N,K], contribution_maps [N,T,H,W] and, if requested, dynamic_linear_weights [N,T,6,H,W]."""
-        if self.head_kind == "gap_fc":
-            targets = ops.check_targets(targets, self.head.cout)
-
-        def columns(logits):
-            tg = targets if self.head_kind == "gap_fc" else ops.check_targets(targets, logits.shape[1])
-            tg = tg.to(device=logits.device, dtype=torch.int64)
-            return (tg.view(1, -1).expand(x.shape[0], -1) if tg.dim() == 1 else tg).unbind(1)
-        return self._explain_repeated(x, columns, lambda st, cls, last: self._backward(x, st, cls.contiguous(), want_weights, consume=last),
-                                      want_weights)
-
-    @torch.no_grad()
-    def explain_functionals(self, x: torch.Tensor, functionals, want_weights: bool = False) -> Dict[str, torch.Tensor]:
-        """ONE forward in explanation mode, then one input-gradient pass per LogitFunctional of `functionals` (each over the whole
-        batch) -- explain_targets for functionals: the kept forward does not depend on what is explained.
-        Returns logits [N, K], functional_values [N, T], contribution_maps [N, T, H, W] and, if requested, dynamic_linear_weights
-        [N, T, 6, H, W]."""
-        fs = [self._checked_functional(x, f) for f in functionals]
-        if not fs or any(f is None for f in fs):
-            raise ValueError("explain_functionals: a non-empty list of LogitFunctional objects")
-        out = self._explain_repeated(x, lambda logits: fs,
-                                     lambda st, f, last: self._backward(x, st, None, want_weights, consume=last, functional=f), want_weights)
-        out["functional_values"] = torch.stack([f.value(out["logits"]) for f in fs], 1)
-        return out
-
-    def _explain_repeated(self, x, make_args, backward, want_weights):
-        with ops.absmax_arena(self._absmax_arena, x.device):
-            return passes.explain_repeated(x, lambda: self._run_forward(x, keep=True), make_args, backward, want_weights)
-
-    def _backward(self, x, st, cls, want_weights: bool, consume: bool, g_head=None, outs=None, functional=None):
-        return _drive(self._backward_gen(x, st, cls, want_weights, consume, g_head, outs, functional))
-
-    def _backward_gen(self, x, st, cls, want_weights: bool, consume: bool, g_head=None, outs=None, functional=None):
+    def _backward_gen(self, x, st, cls, want_weights: bool, consume: bool, outs=None, functional=None, g_head=None):
         """Input-gradient pass of logit[cls[n]] for every image n over the state `st` of a kept forward; `consume` frees
         each saved multiplier as soon as it has been used (last / only pass over this state).  `functional` (instead of `cls`): the
-        pass of sum_k c_k logit[k] -- only its first launch differs."""
+        pass of sum_k c_k logit[k]; `g_head` (attention-pool heads): the pass of a cotangent of the head output -- only the first launch
+        differs."""
         global BOUNDARY_FUSION_CALLS
+        if g_head is not None and self.head_kind == "gap_fc":
+            raise BcosHipError("engine: `cotangent` needs an attention-pool head (CLIP image encoder)")
         if functional is not None and self.head_kind == "attnpool":       # a functional over the embedding coordinates: the dense g_emb
             g_head = functional.as_dense(self.n_logits())
         # A "consumer" owns the g_lin tensors of the layers that read some activation X and can therefore
@@ -871,29 +677,7 @@ class ResNetEngine:
         elif self.head_kind == "attn_unpool":
             consumer = _Consumer(self.ap_vconv, self._attn_unpool_backward(st, g_head, consume), None, None, 0)
         else:
-            # d logit[cls] / d (head lin): one-hot * 1/(T*HW) * head scale
-            hc = self.head
-            rank1_ok = (_HEAD_RANK1 and hc.k == (1, 1) and hc.stride == (1, 1) and hc.padding == (0, 0) and getattr(hc, "groups", 1) == 1
-                        and int(getattr(hc.module, "max_out", 1)) == 1 and hc.w_fwd.shape[-1] % 4 == 0 and hc.w_fwd.shape[-1] == hc.cin)
-            if functional is not None and functional.is_sparse and rank1_ok:
-                # a few classes per image: the rank-one launch with a short sum of weight rows (ops.head_rankm_grad)
-                consumer = _HeadRankMConsumer(functional.classes, st["tf"], hc.w_fwd.view(hc.w_fwd.shape[0], -1), self.logit_temperature,
-                                              coef=functional.coeffs)
-            elif functional is not None:
-                # any functional: its cotangent times the head's scale (ops.head_cotangent_grad, the one-hot tensor's general form, with
-                # its row maxima), then the head's own input-gradient contraction
-                if hc.cout % 4 != 0:
-                    raise BcosHipError(f"engine: the dense head gradient of a functional needs a head width that is a multiple of 4 (got {hc.cout})")
-                g_head = ops.head_cotangent_grad(functional.as_dense(hc.cout), st["tf"], self.logit_temperature)
-                consumer = _Consumer(self.head, g_head, None, None, 0)
-            elif rank1_ok:
-                # ... carried through the head's 1 x 1 convolution at once: the gradient is rank one per image (one class column of
-                # the head's scale x one weight row), a streaming launch instead of the [N, 7, 7, 1000] one-hot tensor, a pass for its
-                # row maxima and a K = 1000 contraction over 999 zero columns
-                consumer = _HeadRank1Consumer(cls, st["tf"], hc.w_fwd.view(hc.w_fwd.shape[0], -1), self.logit_temperature)
-            else:
-                g_head = ops.ensure_absmax(ops.head_onehot_grad(cls, st["tf"], self.logit_temperature))
-                consumer = _Consumer(self.head, g_head, None, None, 0)
+            consumer = head_consumer(self.head, st["tf"], cls, functional, self.logit_temperature, rank1=_HEAD_RANK1)
             if consume:
                 st["tf"] = None
         nb = len(self.blocks)
@@ -959,7 +743,7 @@ class ResNetEngine:
                 else:
                     with ops.image_range_reader(convs[ci - 1].reads_image_range):
                         gl = convs[ci].dgrad.run(gl, h, w, track_absmax=convs[ci - 1].k_dgrad >= ops.F16X2_MIN_K,
-                                                 **_mul_kwargs(rec["ts"][ci - 1]))
+                                                 **mul_kwargs(rec["ts"][ci - 1]))
                 if consume:
                     rec["ts"][ci - 1] = None
             gl = convs[0].expand(gl, rec["tw"][0])
@@ -999,7 +783,7 @@ def _boundary_fusable(consumer, blk, rec, H, W) -> bool:
     its ReLU gate in the low bit of the stored multiplier; no MaxOut, B = 2, f16x2 contraction with the maxima of g_main at hand, both
     weight banks with their pre-split images, contiguous tensors below the 2 GiB of the kernel's 32-bit offsets.  (The call's own
     refusals are mirrored here; one that is met anyway -- BCOS_E_NOSUP -- sends the site to the pair of launches too.)"""
-    if not _BOUNDARY_FUSION or type(consumer) is not _Consumer or not isinstance(consumer.conv, _Conv) or len(blk.convs) < 2:
+    if not _BOUNDARY_FUSION or type(consumer) is not _Consumer or not isinstance(consumer.conv, Conv) or len(blk.convs) < 2:
         return False
     c1, c3 = consumer.conv, blk.convs[-1]
     t3, t2 = rec["ts"][-1], rec["ts"][-2]
@@ -1018,6 +802,30 @@ def _boundary_fusable(consumer, blk, rec, H, W) -> bool:
                 and ops.presplit_static(c1.dgrad.classes[0][8]) and ops.presplit_static(c3.dgrad.classes[0][8])
                 and _l_mode() == "f16x2" and ops.F16X2_MIN_K <= 64 and ops.absmax_of(g1) is not None
                 and ops.absmax_of(g1).numel() == g1.shape[0] * H * W)
+
+
+def head_consumer(head, tf, cls, functional, temperature, rank1=True):
+    """The GAP + 1 x 1 head `head` (a Conv; `tf` its kept scale) as the reader of the last feature map: the consumer that starts the
+    input-gradient pass of logit[cls[n]] -- or of `functional` -- from d logit / d (head lin) = one-hot * 1/(T*HW) * head scale.
+    `rank1=False`: never the rank-one launches (BCOS_HEAD_RANK1=0 of the ResNet plan, for A/B)."""
+    rank1_ok = (rank1 and head.k == (1, 1) and head.stride == (1, 1) and head.padding == (0, 0) and head.groups == 1 and head.max_out == 1
+                and head.w_fwd.shape[-1] % 4 == 0 and head.w_fwd.shape[-1] == head.cin)
+    w = head.w_fwd.view(head.w_fwd.shape[0], -1)
+    if functional is not None and functional.is_sparse and rank1_ok:
+        # a few classes per image: the rank-one launch with a short sum of weight rows (ops.head_rankm_grad)
+        return _HeadRankMConsumer(functional.classes, tf, w, temperature, coef=functional.coeffs)
+    if functional is not None:
+        # any functional: its cotangent times the head's scale (ops.head_cotangent_grad, the one-hot tensor's general form, with
+        # its row maxima), then the head's own input-gradient contraction
+        if head.cout % 4 != 0:
+            raise BcosHipError(f"engine: the dense head gradient of a functional needs a head width that is a multiple of 4 (got {head.cout})")
+        return _Consumer(head, ops.head_cotangent_grad(functional.as_dense(head.cout), tf, temperature), None, None, 0)
+    if rank1_ok:
+        # ... carried through the head's 1 x 1 convolution at once: the gradient is rank one per image (one class column of
+        # the head's scale x one weight row), a streaming launch instead of the [N, 7, 7, 1000] one-hot tensor, a pass for its
+        # row maxima and a K = 1000 contraction over 999 zero columns
+        return _HeadRank1Consumer(cls, tf, w, temperature)
+    return _Consumer(head, ops.ensure_absmax(ops.head_onehot_grad(cls, tf, temperature)), None, None, 0)
 
 
 class _HeadConv:
@@ -1167,13 +975,8 @@ def _linear_geom(rows, cin, cout, out_pitch=0):
 
 
 def attach(net) -> ResNetEngine:
-    """Compile `net` (a BcosifyNetwork around a torchvision-style ResNet) and make `net(x)` (under no_grad) and
-    `net.explain_batch(x)` use the fused plan.  Call `net._bcos_engine.refresh()` after changing parameters."""
-    eng = ResNetEngine(net)
-    object.__setattr__(net, "_bcos_engine", eng)
-    return eng
+    """Compile `net` (a BcosifyNetwork around a torchvision-style ResNet) into the fused plan (bcos_hip/plan.py: attach)."""
+    return plan.attach(net, ResNetEngine)
 
 
-def detach(net):
-    if hasattr(net, "_bcos_engine"):
-        object.__delattr__(net, "_bcos_engine")
+detach = plan.detach

@@ -1837,7 +1837,7 @@ def bn_batch_stats(y2d, weight, eps, running_var=None, momentum=0.0):
     _l.check(_l.load().bcos_bn_batch_stats(_dev(y2d, "y"), _dev(weight, "weight"), _dev(running_var, "running_var"), _dev(mean, "mean"),
                                            _dev(var, "var"), _dev(rstd, "rstd"), _dev(g, "g"), _dev(ws, "workspace"), n, rows, Cc, float(eps),
                                            float(momentum), _stream()), "bcos_bn_batch_stats")
-    if running_var is not None:          # written through its pointer: tell torch (plans keyed on tensor versions re-read it, engine._Conv.fingerprint)
+    if running_var is not None:          # written through its pointer: tell torch (plans keyed on tensor versions re-read it, engine.Conv.fingerprint)
         torch.autograd.graph.increment_version(running_var)
     return mean, var, rstd, g
 

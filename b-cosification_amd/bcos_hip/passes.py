@@ -90,7 +90,7 @@ def _interleave(gens, streams, arenas, device):
 def n_streams(n: int, limit: int, device) -> int:
     """On how many streams does a pass over `n` images run?  At most `limit`, fewer for batches under limit x _SUBBATCH_MIN images, and
     ONE when that leaves no second sub-batch, when the batch is not on a device, and while the caller's stream is being captured into
-    a hipGraph.  The one statement of the rule: every entry point of both engines asks here."""
+    a hipGraph.  The one statement of the rule: every entry point of every plan asks here (plan.FusedPlan.n_streams)."""
     S = min(int(limit), n // _SUBBATCH_MIN)
     if S <= 1 or not _on_device(device) or torch.cuda.is_current_stream_capturing():
         return 1

@@ -14,16 +14,13 @@ producer's epilogue, LayerNorm input-gradients (which also add the residual grad
 scale), and the attention v-gradient kernel.  The last GEMM yields the patch-major input gradient which one kernel turns
 into W(x) [N,6,H,W] and the contribution map.
 """
-from typing import Dict, Optional
-
 import torch
 import torch.nn as nn
 
-from . import ops, passes
-from .engine import _Conv, forward_passes
-from .functional import LogitFunctional, as_functional
+from . import ops, plan
+from .engine import Conv
 from .lib import BCOS_EPI_FORCE_POW, BCOS_LINEAR_EPS, BcosHipError
-from .passes import _drive
+from .plan import FusedPlan
 
 
 class _Lin:
@@ -158,8 +155,9 @@ def _mx(t, src=None):
     return ops.ensure_absmax(t)
 
 
-class ViTEngine:
+class ViTEngine(FusedPlan):
     """Launch plan for `bcosify_vit.BcosifyNetwork(SimpleViT(...))`."""
+    who = "vit engine"
 
     def __init__(self, net):
         from bcos.models.vit import SimpleViT
@@ -167,7 +165,6 @@ class ViTEngine:
         m = net.model
         if not isinstance(m, SimpleViT):
             raise BcosHipError(f"vit engine: {type(m).__name__} is not a SimpleViT")
-        self.net = net
         self.patch = m.patch_size[0]
         if m.patch_size[0] != m.patch_size[1]:
             raise BcosHipError("vit engine: square patches only")
@@ -184,7 +181,7 @@ class ViTEngine:
             for conv, gn, act in zip(mods[0::3], mods[1::3], mods[2::3]):
                 if not isinstance(gn, DetachableGroupNorm2d) or not isinstance(act, (MyGELU, nn.Identity)):
                     raise BcosHipError(f"vit engine: unsupported conv-stem layer ({type(gn).__name__}, {type(act).__name__})")
-                self.stem.append(dict(conv=_Conv(conv, None), gn=gn, gelu=isinstance(act, MyGELU)))
+                self.stem.append(dict(conv=Conv(conv, None), gn=gn, gelu=isinstance(act, MyGELU)))
         self.blocks = []
         for enc in m.transformer.children():
             act = enc.ff.net.act
@@ -202,17 +199,10 @@ class ViTEngine:
         self.head_ln = _LN(m.linear_head.norm)
         self.head = _Lin(m.linear_head.linear)
         self.gap_reorder = bool(m.gap_reorder)
-        norm = net.bcosifynormalize
-        self._mean, self._std = tuple(norm.mean), tuple(norm.std)
-        self._dev = {}
-        ll = net.logit_layer
-        self.logit_bias = ll.logit_bias if ll is not None else None
-        self.logit_temperature = ll.logit_temperature if ll is not None else None
-        self._absmax_arena = ops.AbsmaxArena()      # row maxima of one pass: one zero fill instead of one per tensor
         # three sub-batch streams for the token path (ResNets: two): its launches are shorter -- 394 tiles per half-batch GEMM at batch
         # 512 -- and a third stream fills more of their tails: same-node A/B at ViT-Ti batch 512, three pairs: 18.76 / 18.86 / 18.77 ms
         # against 19.23 / 19.29 / 19.14 with two (ResNet-50: no difference).  Fewer streams for batches under 3 x _SUBBATCH_MIN.
-        self.subbatch_streams, self._side = _VIT_SUBBATCH_STREAMS, passes.SideStreams()
+        super().__init__(net, _VIT_SUBBATCH_STREAMS)
         self.refresh()
 
     def _fingerprint(self):
@@ -268,13 +258,6 @@ class ViTEngine:
         self.head.fold(self.head_ln)
         self._pe = {}
 
-    def _consts(self, device):
-        key = str(device)
-        if key not in self._dev:
-            self._dev[key] = (torch.tensor(self._mean, dtype=torch.float32, device=device),
-                              torch.tensor(self._std, dtype=torch.float32, device=device))
-        return self._dev[key]
-
     def _posemb(self, gh, gw, device):
         key = (gh, gw, str(device))
         if key not in self._pe:
@@ -284,32 +267,13 @@ class ViTEngine:
         return self._pe[key]
 
     # --------------------------------------------------------------------------------------------------------
-    def _run_forward(self, x, keep):
-        return _drive(self._run_forward_gen(x, keep))
-
-    def _run_forward_gen(self, x, keep, occlude=None, perturb=None):
-        """the forward pass as a generator (yields behind the embedding and behind every encoder block: passes._interleave);
-        `occlude` = (bank, first, n): the batch is the n copies of the ONE image x occluded by bank[first:first + n] (forward only);
-        `perturb` = (plan, first, n): the batch is copies [first, first + n) of the perturbed copies of the images x (forward only)"""
-        if x.dim() != 4 or x.shape[1] not in (3, 6):
-            raise ValueError(f"expected [N,6,H,W] (or [N,3,H,W] to be AddInverse-encoded), got {tuple(x.shape)}")
-        ops.require_device(x, "bcos_hip.vit_engine")
-        self._ensure_fresh()
-        x = x.detach()
-        x = x if x.is_contiguous() else x.contiguous()
-        N, _, H, W = x.shape
-        p = self.patch
-        mean, std = self._consts(x.device)
-        add_inverse = x.shape[1] == 3
-        if perturb is not None:
-            N = perturb[2]
-            xn = ops.prep_input_perturbed(x, perturb[0].scores, perturb[0].thr, mean, std, descending=perturb[0].descending,
-                                          first=perturb[1], n=N, cpad=8, want_absmax=_F16X2)
-        elif occlude is None:
-            xn = ops.prep_input(x, mean, std, cpad=8, add_inverse=add_inverse, want_absmax=_F16X2)     # K = 2048 patch embedding
-        else:
-            N = occlude[2]
-            xn = ops.prep_input_occluded(x, occlude[0], mean, std, first=occlude[1], n=N, cpad=8, want_absmax=_F16X2)
+    def _run_forward_gen(self, src, keep, gates=None):
+        """the forward pass over an input source (bcos_hip/plan.py) as a generator (yields behind the embedding and behind every encoder
+        block: passes._interleave)"""
+        if gates is not None:
+            raise BcosHipError("vit engine: replayed gates are not built for this plan")
+        x, xn = self._begin(src, want_absmax=_F16X2)      # (K = 2048 patch embedding)
+        N, p = src.n, self.patch
         stem_st = []
         for layer in self.stem:          # conv stem: B-cos conv, GroupNorm (variance held constant in explanation mode), GELU gate
             hw_in = (xn.shape[1], xn.shape[2])
@@ -330,7 +294,7 @@ class ViTEngine:
         ops.tapconv(xn, self.embed_w, geom, out=tok, scale_out=t_embed, bias=self.embed_bias,
                     bcos_mode=BCOS_LINEAR_EPS if self.embed_b != 1.0 else 0, b=self.embed_b, track_absmax=False)
         ops.add_rows_bcast(tok, self._posemb(gh, gw, x.device))
-        st = dict(x=x, add_inverse=add_inverse, N=N, T=T, t_embed=t_embed, blocks=[], stem=stem_st, tok_hw=(H, W)) if keep else None
+        st = dict(x=x, add_inverse=src.add_inverse, N=N, T=T, t_embed=t_embed, blocks=[], stem=stem_st, tok_hw=(H, W)) if keep else None
         cur = tok
         yield
         for blk in self.blocks:
@@ -376,84 +340,18 @@ class ViTEngine:
             st.update(rstd_h=rstd_h, t_head=t_head)
         return logits, st
 
-    def _prepare(self, x):
-        """everything the passes cache lazily (refreshed plans, constants, the positional-embedding table), brought up to date on the
-        current stream (passes.SideStreams.run)"""
-        self._ensure_fresh()
-        self._consts(x.device)
+    def _prepare_extra(self, x):
+        """the positional-embedding table"""
         if not self.stem and x.dim() == 4:
             self._posemb(x.shape[2] // self.patch, x.shape[3] // self.patch, x.device)
 
-    def _passes(self, x, n, make_gen):
-        """make_gen(lo, hi) over n images as sub-batches on side streams, or once on the caller's (bcos_hip/passes.py: images are
-        independent, the sub-batches fill each other's launch tails)"""
-        with _absmax_policy():
-            return self._side.run(x.device, n, self.subbatch_streams, make_gen, self._absmax_arena, lambda: self._prepare(x))
-
-    @torch.no_grad()
-    def forward(self, x, occlude: Optional[torch.Tensor] = None, perturb=None):
-        """`occlude` (a device bank [n, 4] of int32 rectangles): x is ONE image [1, 6, H, W] and the result the logits [n, classes] of
-        its n occluded copies (engine.ResNetEngine.forward): prepared by ops.prep_input_occluded, then the plan of an n-image batch.
-        `perturb` (bcos_hip.perturbation.PerturbPlan): x is [B, 6, H, W] and the result the logits [B * K, classes], image-major, of its
-        perturbed copies (engine.ResNetEngine.forward): prepared by ops.prep_input_perturbed.  Not together with `occlude`."""
-        return forward_passes(self, x, occlude, perturb)
-
-    @torch.no_grad()
-    def explain(self, x, targets: Optional[torch.Tensor] = None, want_weights: bool = True,
-                functional: Optional[LogitFunctional] = None) -> Dict[str, torch.Tensor]:
-        """`functional` (bcos_hip.functional.LogitFunctional, instead of `targets`): the pass of a linear functional sum_k c_k y_k of the
-        logits (engine.ResNetEngine.explain); the result carries `functional_value` [N] in place of `explained_class_idx`."""
-        x = passes.detached(x)
-        functional = self._checked_functional(x, functional, targets)
-        targets = ops.check_targets(targets, self.head.cout)      # IndexError like the reference's out[0, idx]; negative indices wrap
-        tg = None if targets is None else targets.to(device=x.device, dtype=torch.int64).contiguous()
-        outs = passes.explanation_outputs(x, want_weights)
-
-        def one(lo, hi):
-            return self._explain_gen(x[lo:hi], None if tg is None else tg[lo:hi], want_weights,
-                                     outs=(outs[0][lo:hi] if want_weights else None, outs[1][lo:hi]),
-                                     functional=None if functional is None else functional[lo:hi].to(x.device))
-        return passes.assemble_explanation(self._passes(x, x.shape[0], one), outs)
+    def _pass_context(self):
+        return _absmax_policy()
 
     def n_logits(self) -> int:
         return self.head.cout
 
-    def _checked_functional(self, x, functional, targets=None):
-        """a `functional` argument validated on the host before any launch and moved to x's device (None stays None)"""
-        functional = as_functional(functional)
-        if functional is None:
-            return None
-        if targets is not None:
-            raise ValueError("vit engine: `functional` replaces `targets`: pass one of them")
-        return functional.checked(x.shape[0], self.head.cout).to(x.device)
-
-    @torch.no_grad()
-    def explain_functionals(self, x, functionals, want_weights: bool = False) -> Dict[str, torch.Tensor]:
-        """ONE forward in explanation mode, then one input-gradient pass per LogitFunctional of `functionals`
-        (engine.ResNetEngine.explain_functionals) -> logits [N, K], functional_values [N, T], contribution_maps [N, T, H, W] and, if
-        requested, dynamic_linear_weights [N, T, 6, H, W]."""
-        x = passes.detached(x)
-        fs = [self._checked_functional(x, f) for f in functionals]
-        if not fs or any(f is None for f in fs):
-            raise ValueError("explain_functionals: a non-empty list of LogitFunctional objects")
-        with _absmax_policy(), ops.absmax_arena(self._absmax_arena, x.device):
-            out = passes.explain_repeated(x, lambda: self._run_forward(x, keep=True), lambda logits: fs,
-                                          lambda st, f, last: _drive(self._backward_gen(x, st, None, want_weights, functional=f, consume=last)),
-                                          want_weights)
-        out["functional_values"] = torch.stack([f.value(out["logits"]) for f in fs], 1)
-        return out
-
-    def _explain_gen(self, x, targets, want_weights, outs=None, functional=None):
-        logits, st = yield from self._run_forward_gen(x, keep=True)
-        pred, _ = ops.argmax_rows(logits)
-        if functional is not None:
-            wts, contrib = yield from self._backward_gen(x, st, None, want_weights, outs, functional)
-            return dict(logits=logits, prediction=pred, functional_value=functional.value(logits), dynamic_linear_weights=wts,
-                        contribution_map=contrib)
-        cls = pred if targets is None else targets.to(device=logits.device, dtype=torch.int64).contiguous()
-        wts, contrib = yield from self._backward_gen(x, st, cls, want_weights, outs)
-        return dict(logits=logits, prediction=pred, explained_class_idx=cls, dynamic_linear_weights=wts,
-                    contribution_map=contrib)
+    explain_functionals = FusedPlan._explain_functionals
 
     def _head_grad(self, cls, functional, scale):
         """gradient of the explained output w.r.t. the head's `lin` (scale [N, R, 1, K] -> [N, R, 1, K]): the one-hot tensor of a class
@@ -465,9 +363,11 @@ class ViTEngine:
             raise BcosHipError(f"vit engine: the dense head gradient of a functional needs a head width that is a multiple of 4 (got {K})")
         return ops.head_cotangent_grad(functional.as_dense(K), scale, self.logit_temperature, want_absmax=_F16X2)
 
-    def _backward_gen(self, x, st, cls, want_weights, outs=None, functional=None, consume=True):
+    def _backward_gen(self, x, st, cls, want_weights, consume, outs=None, functional=None, g_head=None):
         """input-gradient pass of logit[cls[n]] -- or of `functional` -- over the state of a kept forward; `consume` frees each block's
         saved tensors once used (the last / only pass over this state)"""
+        if g_head is not None:
+            raise BcosHipError("vit engine: `cotangent` needs an attention-pool head (CLIP image encoder)")
         N, T = st["N"], st["T"]
         nb = len(self.blocks)
         t_last = st["blocks"][-1]["t2"] if nb else st["t_embed"]
@@ -544,6 +444,7 @@ class ViTEngine:
 
 
 def attach(net) -> ViTEngine:
-    eng = ViTEngine(net)
-    object.__setattr__(net, "_bcos_engine", eng)
-    return eng
+    return plan.attach(net, ViTEngine)
+
+
+detach = plan.detach

@@ -281,7 +281,8 @@ def test_plan_launch_list_is_the_recorded_execution_order(monkeypatch):
     for keep in (False, True):
         monkeypatch.setattr(densenet_engine, "PLAN_LOG", [])
         from bcos_hip.passes import _drive
-        _drive(eng._run_forward_gen(synth.synthetic_images(1, seed=5), keep=keep))
+        from bcos_hip.plan import Images
+        _drive(eng._run_forward_gen(Images(synth.synthetic_images(1, seed=5)), keep=keep))
         assert densenet_engine.PLAN_LOG == expect, keep
 
 

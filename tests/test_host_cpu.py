@@ -126,6 +126,13 @@ def test_targets_are_validated_on_the_host():
     from bcos_hip import engine, vit_engine
     assert "check_targets" in inspect.getsource(engine.ResNetEngine.explain) and "check_targets" in inspect.getsource(engine.ResNetEngine.explain_targets)
     assert "check_targets" in inspect.getsource(vit_engine.ViTEngine.explain)
+    # (the entry points are inherited from plan.FusedPlan; the check they call ahead of every launch is ops.check_targets)
+    from bcos_hip import plan
+    assert engine.ResNetEngine.explain is plan.FusedPlan.explain is vit_engine.ViTEngine.explain
+    for fn in (plan.FusedPlan.explain, plan.FusedPlan._explain_targets):
+        src = inspect.getsource(fn)
+        assert 0 < src.index("self._check_targets(targets)") < min(src.index(w) for w in ("_passes", "_explain_repeated") if w in src)
+    assert all("ops.check_targets(" in inspect.getsource(c._check_targets) for c in (plan.FusedPlan, engine.ResNetEngine))
 
 
 def test_telemetry_samples_the_physical_device():
@@ -983,7 +990,7 @@ def check_frozen_batchnorm_and_maxout(device, tol_out, tol):
             changed += int(not torch.equal(a, before[k]))
         assert (changed == 0) if frozen == "all" else (changed > 0)
 
-    # -- a fused MaxOut node (engine._Conv.max_out) is refused by the plan BEFORE any buffer has been touched
+    # -- a fused MaxOut node (engine.Conv.max_out) is refused by the plan BEFORE any buffer has been touched
     net = synth.build_bcosified_resnet("resnet18")
     blk = net.model.layer3[1]
     blk.conv2 = BcosifyConv2d(256, 256, 3, 1, 1, max_out=2, b=2)
@@ -1011,7 +1018,7 @@ def _engine_exec_trace(arch, monkeypatch, device="cpu"):
     eng = engine.attach(net)
     names = {m: n for n, m in net.named_modules()}
     calls = []
-    orig = engine._Conv.fwd
+    orig = engine.Conv.fwd
 
     def fwd(self, x, **kw):
         y, t = orig(self, x, **kw)
@@ -1019,7 +1026,7 @@ def _engine_exec_trace(arch, monkeypatch, device="cpu"):
         calls.append([names[self.module], names.get(self.bn), nchw(x), nchw(y), kw.get("addend") is not None, bool(kw.get("relu"))])
         return y, t
 
-    monkeypatch.setattr(engine._Conv, "fwd", fwd)
+    monkeypatch.setattr(engine.Conv, "fwd", fwd)
     pools = []
     orig_pool = ops.avgpool2d_fwd
     monkeypatch.setattr(ops, "avgpool2d_fwd", lambda a, k, s_, p_, **kw: (pools.append([list(a.shape), k, s_, p_]), orig_pool(a, k, s_, p_, **kw))[1])

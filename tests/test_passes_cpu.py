@@ -217,16 +217,16 @@ def small_vit():
 def relu_gates(eng, x, monkeypatch):
     """random 0/1 gates of the shapes of the engine's ReLUs for the batch x, in execution order"""
     from bcos_hip import engine
-    shapes, inner = [], engine._Conv.fwd
+    shapes, inner = [], engine.Conv.fwd
 
     def fwd(self, a, **kw):
         y, t = inner(self, a, **kw)
         if kw.get("relu"):
             shapes.append(tuple(y.shape))
         return y, t
-    monkeypatch.setattr(engine._Conv, "fwd", fwd)
+    monkeypatch.setattr(engine.Conv, "fwd", fwd)
     eng.forward(x)
-    monkeypatch.setattr(engine._Conv, "fwd", inner)
+    monkeypatch.setattr(engine.Conv, "fwd", inner)
     g = torch.Generator().manual_seed(11)
     return [(torch.rand(s, generator=g) > 0.3).float() for s in shapes]
 

@@ -208,19 +208,20 @@ def test_harness_asks_an_attached_engine_for_perturbed_forwards(monkeypatch):
 
 def test_forward_refuses_perturb_together_with_occlude():
     from bcos_hip import engine, perturbation as P, vit_engine
+    from bcos_hip.plan import input_source
     x = torch.zeros(1, 6, 4, 4)
     plan = P.PerturbPlan(torch.zeros(1, 16), torch.zeros(1, 2, dtype=torch.int64))
     bank = torch.tensor([[0, 2, 0, 2]], dtype=torch.int32)
     with pytest.raises(ValueError, match="one of the two"):
-        engine.forward_passes(None, x, occlude=bank, perturb=plan)
+        input_source(x, occlude=bank, perturb=plan)
     for cls in (engine.ResNetEngine, vit_engine.ViTEngine):
         with pytest.raises(ValueError, match="one of the two"):
             cls.forward(object.__new__(cls), x, occlude=bank, perturb=plan)
     from bcos_hip.lib import BcosHipError
     with pytest.raises(ValueError, match="6-channel"):
-        engine.forward_passes(None, x[:, :3], perturb=plan)
+        input_source(x[:, :3], perturb=plan)
     with pytest.raises(BcosHipError):                                  # no CPU path
-        engine.forward_passes(None, x, perturb=plan)
+        input_source(x, perturb=plan)
 
 
 # ---------------------------------------------------------------------------------------------------------------------- ABI
