@@ -344,8 +344,8 @@ class DenseNetEngine(FusedPlan):
                                    "detach() the engine and use the module path, or a ResNet / ViT engine")
 
     @torch.no_grad()
-    def forward(self, x: torch.Tensor, occlude=None, perturb=None) -> torch.Tensor:
-        self._refuse(occlude=occlude, perturb=perturb)
+    def forward(self, x: torch.Tensor, occlude=None, perturb=None, rise=None) -> torch.Tensor:
+        self._refuse(occlude=occlude, perturb=perturb, rise=rise)
         return super().forward(x)
 
     @torch.no_grad()

@@ -19,7 +19,7 @@ LIB_PATH = Path(os.environ["BCOS_HIP_LIB"]) if os.environ.get("BCOS_HIP_LIB") el
 CSRC = PKG_ROOT / "csrc"
 INCLUDE = REPO_ROOT / "include"
 SOURCES = ["bcos_tapconv.hip", "bcos_skinny.hip", "bcos_elementwise.hip", "bcos_vit.hip", "bcos_render.hip", "bcos_train.hip",
-           "bcos_agc.hip", "bcos_occlusion.hip", "bcos_perturb.hip", "bcos_head.hip", "bcos_boundary.hip", "bcos_dense.hip", "bcos_abi.hip"]
+           "bcos_agc.hip", "bcos_occlusion.hip", "bcos_rise.hip", "bcos_perturb.hip", "bcos_head.hip", "bcos_boundary.hip", "bcos_dense.hip", "bcos_abi.hip"]
 
 BCOS_NONE, BCOS_CONV_EPS, BCOS_LINEAR_EPS = 0, 1, 2
 BCOS_EPI_NORM_ONLY = 1
@@ -187,6 +187,9 @@ SIGNATURES = {
     "bcos_agc_clip": (C.c_int, [C.POINTER(AgcTensor), _I, _F, _F, _P]),
     "bcos_prep_input_occluded": (C.c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "bcos_occlusion_accumulate": (C.c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "bcos_rise_masks": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "bcos_prep_input_rise": (C.c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "bcos_rise_accumulate": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P]),
     "bcos_boundary_conv3_grad": (C.c_int, [C.POINTER(BoundaryConv3), _P]),
     "bcos_perturb_select_ws_bytes": (C.c_int, [_I, _L, _I, C.POINTER(C.c_int64)]),
     "bcos_perturb_select": (C.c_int, [_P, _P, _I, _P, _P, _L, _I, _L, _I, _P]),
@@ -202,7 +205,7 @@ _lib = None
 def build(force: bool = False, verbose: bool = False) -> Path:
     """Compile csrc/*.hip for gfx950 into lib/libbcos_hip.so (hipcc cross-compiles without a GPU)."""
     srcs = [CSRC / s for s in SOURCES]
-    deps = srcs + [CSRC / "bcos_internal.h", INCLUDE / "bcos_hip.h"]
+    deps = srcs + [CSRC / "bcos_rise_mask.h", CSRC / "bcos_internal.h", INCLUDE / "bcos_hip.h"]
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     # the compiler flags are part of the build's identity: objects (and the library) built with other BCOS_HIPCC_FLAGS are
     # never reused -- the flags are recorded in a stamp file next to the objects and a change forces a full rebuild
@@ -229,7 +232,7 @@ def build(force: bool = False, verbose: bool = False) -> Path:
         for k in parts:
             obj = objdir / (s.stem + ("" if k is None else f"_p{k}") + ".o")
             extra = [] if k is None else [f"-DBCOS_TAPCONV_PART={k}"]
-            stale = force or not obj.exists() or any(obj.stat().st_mtime < d.stat().st_mtime for d in (s, deps[-2], deps[-1]))
+            stale = force or not obj.exists() or any(obj.stat().st_mtime < d.stat().st_mtime for d in (s, deps[-3], deps[-2], deps[-1]))
             jobs.append((obj, [hipcc] + flags + extra + ["-c", str(s), "-o", str(obj)], stale))
     from concurrent.futures import ThreadPoolExecutor
 

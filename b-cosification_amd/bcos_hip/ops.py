@@ -1150,6 +1150,99 @@ def occlusion_accumulate(org, pert, rects, H, W, targets=None, only_positive=Fal
     return out
 
 
+class RiseBank:
+    """A bank of RISE masks (include/bcos_hip.h, "RISE baseline explainer"): `rows`, a contiguous int32 tensor [n, 4] of
+    (bits_lo, bits_hi, shift_r, shift_c); `s`, the side of the bit grid; `host`, the rows' copy in host memory (what bcos_rise_accumulate
+    validates; made on first use if not given).  bank[lo:hi] is the bank of those rows (a view), bank.to(device) a bank there."""
+
+    def __init__(self, rows, s, host=None):
+        self.rows, self.s, self._host = rows, int(s), host
+
+    @property
+    def host(self):
+        if self._host is None:
+            self._host = self.rows.detach().cpu().contiguous()
+        return self._host
+
+    def __len__(self):
+        return int(self.rows.shape[0])
+
+    def __getitem__(self, key):
+        if not isinstance(key, slice) or key.step not in (None, 1):
+            raise TypeError("RiseBank: only contiguous slices bank[lo:hi]")
+        return RiseBank(self.rows[key], self.s, None if self._host is None else self._host[key])
+
+    def to(self, device):
+        return RiseBank(self.rows.to(device), self.s, self.host)
+
+
+def _rise_bank(bank, what, first=0, n=None):
+    """-> (rows, s, first, n) of a RiseBank after the host checks the three wrappers share"""
+    rows = getattr(bank, "rows", None)
+    if not (torch.is_tensor(rows) and rows.dtype == torch.int32 and rows.dim() == 2 and rows.shape[1] == 4 and rows.is_contiguous()
+            and rows.shape[0] > 0 and isinstance(getattr(bank, "s", None), int)):
+        raise BcosHipError(f"{what}: a mask bank is a RiseBank: contiguous int32 rows [n, 4] of (bits_lo, bits_hi, shift_r, shift_c) and s")
+    if not 2 <= bank.s <= 8:
+        raise BcosHipError(f"{what}: s must be in 2..8, got {bank.s}")
+    first = int(first)
+    n = rows.shape[0] - first if n is None else int(n)
+    if first < 0 or n <= 0 or first + n > rows.shape[0]:
+        raise BcosHipError(f"{what}: masks [{first}, {first + n}) of a bank of {rows.shape[0]}")
+    return rows, bank.s, first, n
+
+
+def rise_masks(bank, H, W, first=0, n=None):
+    """The dense masks [n, H, W] of rows [first, first + n) of a device RiseBank (include/bcos_hip.h: bcos_rise_masks) -- for tests and
+    for callers without a fused engine; an engine never builds them."""
+    lib = _l.load()
+    rows, s, first, n = _rise_bank(bank, "rise_masks", first, n)
+    if not rows.is_cuda:
+        raise BcosHipError(f"rise_masks: the mask bank is on {rows.device}; the kernels only exist for HIP devices (no CPU fallback)")
+    out = torch.empty((n, int(H), int(W)), device=rows.device, dtype=torch.float32)
+    _l.check(lib.bcos_rise_masks(C.c_void_p(rows.data_ptr()), _dev(out, "out"), rows.shape[0], first, n, s, int(H), int(W), _stream()),
+             "bcos_rise_masks")
+    return out
+
+
+def prep_input_rise(x_nchw, bank, mean6, std6, first=0, n=None, cpad=8, want_absmax=False):
+    """The prepared input [n, H, W, cpad] of the copies of ONE image x_nchw [1, 6, H, W] under masks [first, first + n) of a device
+    RiseBank: what prep_input returns for `x_nchw * m_i`, bit for bit, from one launch that stores neither the masks nor the masked
+    batch (include/bcos_hip.h: bcos_prep_input_rise)."""
+    lib = _l.load()
+    rows, s, first, n = _rise_bank(bank, "prep_input_rise", first, n)
+    if x_nchw.dim() != 4 or x_nchw.shape[0] != 1:
+        raise BcosHipError(f"prep_input_rise: one image [1, 6, H, W] at a time, got {tuple(x_nchw.shape)}")
+    if not rows.is_cuda or rows.device != x_nchw.device:
+        raise BcosHipError(f"prep_input_rise: the mask bank is on {rows.device}, the image on {x_nchw.device}")
+    _, Cx, H, W = x_nchw.shape
+    out = torch.empty((n, H, W, cpad), device=x_nchw.device, dtype=torch.float32)
+    am = _fused_absmax(out, want_absmax)
+    _l.check(lib.bcos_prep_input_rise(_dev(x_nchw, "x"), C.c_void_p(rows.data_ptr()), _dev(out, "out"), _dev(mean6, "mean"),
+                                      _dev(std6, "std"), C.c_void_p(am.data_ptr()) if am is not None else None, rows.shape[0], first, n,
+                                      s, Cx, H, W, cpad, 0, _stream()), "bcos_prep_input_rise")
+    return out
+
+
+def rise_accumulate(scores, bank, H, W, p1):
+    """scores [n, T] (class scores of the n masked copies, on the device), bank (device RiseBank of n rows) -> out [T, H, W]:
+    (sum_i scores[i, t] * m_i) / n / p1 in the fixed fp32 order of include/bcos_hip.h (bcos_rise_accumulate; rise.py:93-95).  The
+    bank's host copy is validated by the library."""
+    lib = _l.load()
+    rows, s, _, n = _rise_bank(bank, "rise_accumulate")
+    if not (torch.is_tensor(scores) and scores.dim() == 2 and scores.shape[0] == n and scores.shape[1] > 0):
+        raise BcosHipError(f"rise_accumulate: scores [{n}, T] for a bank of {n} masks, got {tuple(getattr(scores, 'shape', ()))}")
+    if not rows.is_cuda or rows.device != scores.device:
+        raise BcosHipError(f"rise_accumulate: the mask bank is on {rows.device}, the scores on {scores.device}")
+    host = bank.host
+    if host.is_cuda or host.dtype != torch.int32 or tuple(host.shape) != (n, 4) or not host.is_contiguous():
+        raise BcosHipError("rise_accumulate: the bank's host copy must be its contiguous int32 rows in host memory")
+    T = scores.shape[1]
+    out = torch.empty((T, int(H), int(W)), device=scores.device, dtype=torch.float32)
+    _l.check(lib.bcos_rise_accumulate(_dev(scores, "scores"), C.c_void_p(rows.data_ptr()), C.c_void_p(host.data_ptr()), _dev(out, "out"),
+                                      n, T, s, int(H), int(W), float(p1), _stream()), "bcos_rise_accumulate")
+    return out
+
+
 PERTURB_MAX_COUNTS = 64            # include/bcos_hip.h: BCOS_PERTURB_MAX_COUNTS
 _PERTURB_WS = {}                   # (device, stream) -> workspace of perturb_select (launches of one stream run in order: one buffer)
 

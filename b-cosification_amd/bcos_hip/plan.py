@@ -88,10 +88,35 @@ class PerturbedCopies(OccludedCopies):
                                         first=self.first, n=self.n, cpad=8, want_absmax=want_absmax)
 
 
-def input_source(x, occlude=None, perturb=None):
-    """the source forward(x, occlude=..., perturb=...) reads, validated on the host before anything else happens"""
-    if occlude is not None and perturb is not None:
+class RiseCopies(OccludedCopies):
+    """forward(x, rise=bank): the n copies `x * m_i` of the ONE 6-channel device image x under the RISE masks of bank, an ops.RiseBank
+    (`rows`: a device int32 tensor [n, 4] of (bits_lo, bits_hi, shift_r, shift_c), and the grid side `s`; include/bcos_hip.h).  Neither
+    the masks nor the copies are built: ops.prep_input_rise prepares the input from x and the bank.  Cut along the copy index."""
+
+    def __init__(self, x, bank):
+        if x.dim() != 4 or x.shape[0] != 1 or x.shape[1] != 6:
+            raise ValueError(f"forward(x, rise=...): expected ONE 6-channel image [1,6,H,W] (the masks multiply the network input; "
+                             f"masking before AddInverse is a different operator), got {tuple(x.shape)}")
+        ops.require_device(x, "bcos_hip.engine")
+        rows, s = getattr(bank, "rows", None), getattr(bank, "s", None)
+        if not (torch.is_tensor(rows) and rows.device == x.device and rows.dtype == torch.int32 and rows.dim() == 2      # (x is on a device)
+                and rows.shape[1] == 4 and rows.is_contiguous() and rows.shape[0] > 0 and isinstance(s, int) and 2 <= s <= 8):
+            raise ValueError("forward(x, rise=...): the mask bank is an ops.RiseBank: contiguous int32 rows [n, 4] of (bits_lo, bits_hi, "
+                             "shift_r, shift_c) on the image's device, and the grid side s in 2..8")
+        self.x, self.bank, self.first, self.n = passes.detached(x), bank, 0, rows.shape[0]
+
+    def prepare(self, mean, std, want_absmax):
+        return ops.prep_input_rise(self.x, self.bank, mean, std, first=self.first, n=self.n, cpad=8, want_absmax=want_absmax)
+
+
+def input_source(x, occlude=None, perturb=None, rise=None):
+    """the source forward(x, occlude=..., perturb=..., rise=...) reads, validated on the host before anything else happens"""
+    if occlude is not None and perturb is not None and rise is None:
         raise ValueError("forward(x, occlude=..., perturb=...): one of the two at a time")
+    if rise is not None:
+        if occlude is not None or perturb is not None:
+            raise ValueError("forward(x, occlude=..., perturb=..., rise=...): one of the three at a time")
+        return RiseCopies(x, rise)
     if perturb is not None:
         return PerturbedCopies(x, perturb)
     return Images(x) if occlude is None else OccludedCopies(x, occlude)
@@ -169,15 +194,18 @@ class FusedPlan:
 
     # ---------------------------------------------------------------------------------------------- entry points
     @torch.no_grad()
-    def forward(self, x: torch.Tensor, occlude: Optional[torch.Tensor] = None, perturb=None) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, occlude: Optional[torch.Tensor] = None, perturb=None, rise=None) -> torch.Tensor:
         """The head output of the batch x.
         `occlude` (a device bank [n, 4] of int32 rectangles, include/bcos_hip.h): x is ONE 6-channel image [1, 6, H, W] and the result
         the head output [n, ...] of its n occluded copies `x * mask_i` (occlusion.py:80-90) -- the copies are never built: the prepared
         input comes from ops.prep_input_occluded, everything behind it is the plan of an n-image batch, sub-batch streams included.
         `perturb` (bcos_hip.perturbation.PerturbPlan: scores [B, H*W], thr [B, K], descending, K): x is [B, 6, H, W] and the result the
         head output [B * K, ...], image-major, of the copies with the first k_j pixels of every image's ranking removed -- prepared by
-        ops.prep_input_perturbed, then the plan of a B * K-image batch, cut along the copy index.  Not together with `occlude`."""
-        src = input_source(x, occlude, perturb)
+        ops.prep_input_perturbed, then the plan of a B * K-image batch, cut along the copy index.
+        `rise` (ops.RiseBank: device rows [n, 4] and the grid side s): x is ONE 6-channel image and the result the head output [n, ...]
+        of its copies `x * m_i` under the bank's RISE masks (rise.py:79-88) -- prepared by ops.prep_input_rise from the image and the
+        four integers of every mask, then the plan of an n-image batch.  At most one of the three."""
+        src = input_source(x, occlude, perturb, rise)
 
         def one(lo, hi):
             return (yield from self._run_forward_gen(src.cut(lo, hi), keep=False))[0]

@@ -913,6 +913,56 @@ int bcos_prep_input_occluded(const float* x, const int32_t* rects, float* out, c
 int bcos_occlusion_accumulate(const float* org, const float* pert, const int32_t* rects, const int32_t* rects_host,
                               const int32_t* targets, float* out, int n, int CL, int T, int H, int W, int only_positive, void* stream);
 
+/* -- RISE baseline explainer (additive entry points of ABI v12) -------------------------------------------------------------- */
+/* A RISE mask (interpretability/explanation_methods/explainers/rise.py:34-57 of the reference) is an s x s random 0/1 grid, upsampled
+ * bilinearly to (s + 1) * cell pixels per side and cropped at a random shift.  It is fully described by four int32, so a mask bank is a
+ * DEVICE array [n, 4], 16-byte aligned, of rows (bits_lo, bits_hi, shift_r, shift_c), and the mask VALUES are computed where they are
+ * used.  THE MASK, stated here once (one __device__ function, csrc/bcos_rise_mask.h, serves the three kernels):
+ *   grid     cell g[a, b] in {0, 1} (a: row) is bit a * s + b of the 64-bit word bits_hi:bits_lo; 2 <= s <= 8; bits at and above s * s
+ *            are zero.
+ *   sizes    cell_h = ceil(H / s), cell_w = ceil(W / s); 0 <= shift_r < cell_h, 0 <= shift_c < cell_w; U_h = (s + 1) * cell_h,
+ *            U_w = (s + 1) * cell_w; 2 * U < 2^24 on both axes.
+ *   axis     for pixel row r: p = r + shift_r, U = U_h (columns alike): num = (2 p + 1) * s - U (an integer); i0 = floor(num / (2 U)) by
+ *            integer floor division (it can be -1); f = float(num - i0 * 2 U) / float(2 U), ONE fp32 division of two integers fp32
+ *            holds exactly; the indices i0 and i0 + 1 are mirrored without repeating the edge: k -> |k|, then k >= s -> 2 (s - 1) - k.
+ *   value    with row indices a0, a1 and weight fr, column indices b0, b1 and weight fc, in plain fp32 without contraction:
+ *                top = g[a0,b0] + fc * (g[a0,b1] - g[a0,b0]);  bot = g[a1,b0] + fc * (g[a1,b1] - g[a1,b0]);  m = top + fr * (bot - top)
+ *            Four equal corners give exactly 0 or 1.
+ * This is `resize(grid, up_size, order=1, mode="reflect", anti_aliasing=False)[x : x + H, y : y + W]` of rise.py:53-55 with x = shift_r,
+ * y = shift_c: the sample positions of scipy.ndimage.zoom(grid, U / s, order=1, mode="mirror", grid_mode=True), which current skimage
+ * calls for these arguments. */
+
+/* out[i, r, c] = m_{first + i}(r, c) for the bank rows [first, first + n): the dense masks, for tests and for callers without a fused
+ * engine -- never on an engine's path.  bank: device [n_bank, 4]; out: [n, H, W].
+ * BCOS_E_INVAL: a NULL pointer, s outside 2..8, H / W / n / n_bank <= 0, first < 0 or first + n > n_bank, H * W > 2^31 - 1, 2 U >= 2^24,
+ * a misaligned bank. */
+int bcos_rise_masks(const int32_t* bank, float* out, int n_bank, int first, int n, int s, int H, int W, void* stream);
+
+/* The prepared network input of copies [first, first + n) of ONE image under the bank's masks: what bcos_prep_input writes for the
+ * materialised `x * m_i` (one fp32 product per element, rise.py:79, then the 6-channel Normalize), bit for bit and absmax_out included,
+ * without the masks or the [n, 6, H, W] batch ever being stored.  x: [1,6,H,W] NCHW; bank: device [n_bank, 4]; out: [n,H,W,Cpad],
+ * channels >= 6 zero; absmax_out (NULL or [n*H*W]): per-pixel max |out| bit patterns, as bcos_prep_input.  One thread per output pixel,
+ * 16-byte stores for Cpad == 8; a wavefront reads its copy's bank row through one uniform load (per lane only where a wavefront
+ * straddles two copies); the source pixel is re-read per copy (L2).  64-bit offsets.
+ * BCOS_E_INVAL: as bcos_rise_masks, and Cpad < 6, Cx != 6 or add_inverse != 0 (masking before AddInverse is another operator). */
+int bcos_prep_input_rise(const float* x, const int32_t* bank, float* out, const float* mean6, const float* std6, uint32_t* absmax_out,
+                         int n_bank, int first, int n, int s, int Cx, int H, int W, int Cpad, int add_inverse, void* stream);
+
+/* The saliency maps of rise.py:93-95 from class scores that stayed on the device:
+ *   out[t, r, c] = (sum_i scores[i, t] * m_i(r, c)) / float(n) / p1          scores [n, T], bank device [n, 4], out [T, H, W]
+ * THE ORDER is fixed, all in fp32: the masks are taken in consecutive chunks of 64; a chunk's sum starts at 0 and adds, in ascending i,
+ * the separately rounded products scores[i, t] * m_i (no fused multiply-add); the total starts at 0 and adds the chunk sums in ascending
+ * chunk order; then two correctly rounded divisions.  No atomics: the bits of a map do not depend on T, on which other targets ride
+ * along or on the launch shape.  NO TERM IS SKIPPED: the product is formed for every mask, also where m_i = 0, so a NaN score makes the
+ * WHOLE map of its target NaN (0 * NaN), as does an infinite one wherever its mask is 0; other targets are not touched.
+ * bank_host (NULL or a HOST copy of the bank) is what the call validates, since the library never reads device memory: BCOS_E_INVAL for
+ * a shift outside its cell or grid bits at or above s * s; with NULL the caller vouches for the bank (a shift is then clamped into its
+ * cell).  BCOS_E_INVAL also: a NULL scores / bank / out, n / T / H / W <= 0, s outside 2..8, p1 not positive and finite, the size limits
+ * of bcos_rise_masks, a misaligned bank.  BCOS_E_NOSUP: ceil(H / s) + ceil(W / s) > 3546 (the per-axis tables live in LDS), H > 65535 * 8
+ * or T > 65535 * 8. */
+int bcos_rise_accumulate(const float* scores, const int32_t* bank, const int32_t* bank_host, float* out, int n, int T, int s, int H, int W,
+                         float p1, void* stream);
+
 /* -- block-boundary gradient fused with conv3's input gradient (additive entry point of ABI v12) ---------------------------- */
 /* For an identity-shortcut bottleneck boundary (widths C1 = 64, C4 = 256; M = N * PQ rows) ONE launch computes what two bcos_tapconv_ops
  * launches compute -- the input gradient of the upper block's conv1 with mul / addend / out2 (BCOS_EPI_GATE2_FROM_MUL), then the input
