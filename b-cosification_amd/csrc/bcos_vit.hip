@@ -1314,7 +1314,10 @@ extern "C" int bcos_add_rows_bcast(float* x, const float* pe, int64_t total, int
 static int attn_launch(bool bwd, const float* qkv, const float* z, float* out, float* stats_out, const float* stats_in,
                        unsigned* absmax_out, int B, int T, int H, float scale, void* stream) {
     const int Tpad = (T + 31) & ~31;
-    // f16 matrix pipe (default) or the exact-fp32 MFMA form of rounds 1-2 (BCOS_OPT_ATTENTION_F32; also what the f32 contraction mode means)
+    // f16 matrix pipe (default) or the exact-fp32 MFMA form of rounds 1-2.  BCOS_OPT_ATTENTION_F32 ALONE selects the fp32 kernels: the
+    // contraction mode (bcos_set_contraction_mode) is not consulted here, an f32 contraction mode still runs attention on the f16 pipe.
+    // The fall-through below the h2 launch is never taken today (the fp16 planes fit wherever the fp32 images do: Tpad <= 288 both);
+    // both families are held to the same per-element bounds (include/bcos_hip.h: bcos_attention_fwd).
     if (!bcos_option(BCOS_OPT_ATTENTION_F32)) {
         const size_t hb = 2 * (size_t)Tpad * AH_XROW + 2 * (size_t)DH * (Tpad * 2 + 16) + ((size_t)Tpad + 2 * DH + 2 * (size_t)Tpad) * 4;
         if (hb <= 160 * 1024 && Tpad <= 32 * AH_MAXIT) {

@@ -804,7 +804,26 @@ int bcos_add_rows_bcast(float* x, const float* pe, int64_t total, int64_t period
 
 /* softmax(q k^T * scale) v per (batch, head), head dim 64.  qkv [B, T, 3*H*64] ordered (q | k | v) x (h d) like
  * vit.py:145-146; out [B, T, H*64]; stats (NULL or [B, H, T, 2]) = (row max, 1 / row sum) for the backward.
- * out_absmax (NULL or [B*T], ZERO-FILLED by the caller, ABI v5): row maxima of out (one atomic max per head and row). */
+ * out_absmax (NULL or [B*T], ZERO-FILLED by the caller, ABI v5): row maxima of out (one atomic max per head and row).
+ * T <= 288 (the operands of a head stay in LDS), otherwise BCOS_E_NOSUP.
+ *
+ * Two kernel families compute this and bcos_attention_bwd_v: the default on the f16 matrix pipe (attention_h2_kernel: scaled two-way
+ * fp16 splits, base-2 online softmax) and, with BCOS_OPT_ATTENTION_F32 = 1, the fp32 matrix pipe (attention_mfma_kernel).  The option
+ * alone selects the fp32 kernels; the contraction mode has no part in it.  `stats` means the same thing for both -- the NATURAL-log
+ * row maximum of scale q k^T and the reciprocal of sum_k exp(s - max) -- so statistics of one family may feed the backward of the other.
+ *
+ * Accuracy, per element, both families (tests/attention_cases.py, tests/test_attention_gpu.py).  Against the same expressions in fp64
+ * from the fp32 inputs (s = scale q k^T, m = rowmax s, l = sum_k exp(s - m), p = exp(s - m) / l, out = p v, gv = p^T gout), with
+ * u = 2^-24 and delta[q] = scale ||q||_2 max_k ||k||_2, the Cauchy-Schwarz size of a score of row q:
+ *     |out - out64|[q, d]     <=  7.2 u ( (2 delta[q] + 4) (p64 |v|)[q, d] + max_k |v[k, d]| )
+ *     |gv - gv64|[k, d]       <=  8.0 u ( sum_q p64[q, k] (2 delta[q] + 4) |gout[q, d]| + max(1, sum_q p64[q, k]) max_q |gout[q, d]| )
+ *     |stats[.., 0] - m64|    <= 22.8 u ( delta + |m64| )
+ *     |stats[.., 1] l64 - 1|  <= 14.8 u ( 2 delta + 4 )
+ * (gv from the statistics of the same family's forward).  2 delta is a score error carried through the softmax, + 4 the exponential
+ * and the normalisation; the column-maximum term is the per-feature power of two of the value operand on the f16 pipe: an element
+ * of v / gout is resolved relative to its column's maximum, not to itself.  Each constant is 4 x the worst use of its form by a
+ * plain fp32 evaluation of the same expression over the test's case table (token counts 1 .. 288, token and feature magnitudes
+ * spread over 3 / 8 decades, outliers, score maxima far beyond exp's fp32 range, all-negative scores next to zero padding). */
 int bcos_attention_fwd(const float* qkv, float* out, float* stats, uint32_t* out_absmax, int B, int T, int H, int Dh, float scale,
                        void* stream);
 
