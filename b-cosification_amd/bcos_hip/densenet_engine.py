@@ -23,7 +23,7 @@ Kept between the passes: X of every block (the features AND the source of every 
 multiplier (or what it is rebuilt from) per layer, the transition / classifier / stem scales.  Rebuilt: every pre-activation.
 Scope: groups = 1, no MaxOut, B = 2 fixed, eval mode, BatchNormUncentered2d with or without bias; anything else makes attach() raise
 BcosHipError (the module path keeps working).  Occlusion, perturbation, functionals, replayed gates and cotangents are not built here.
-Training goes per layer through the modules' autograd functions, as for any module graph.
+Training (net.train() + autograd with the engine attached) is bcos_hip/densenet_train_plan.py: one autograd node over this layer list.
 """
 from typing import Dict, List, Optional
 
@@ -97,6 +97,7 @@ class _Layer:
                 raise BcosHipError(f"densenet engine: `{name}` has no `{attr}`: not a torchvision _DenseLayer")
         if not isinstance(layer.relu1, nn.ReLU) or not isinstance(layer.relu2, nn.ReLU):
             raise BcosHipError(f"densenet engine: `{name}` without its ReLUs (act_layer = False) runs through the module path only")
+        self.module = layer
         self.pre = _PreNorm(layer.norm1, f"{name}.norm1")
         self.conv1 = _conv(layer.conv1, layer.norm2, f"{name}.conv1", f"{name}.norm2")
         self.conv2 = _conv(layer.conv2, None, f"{name}.conv2")
@@ -171,7 +172,12 @@ class DenseNetEngine(FusedPlan):
                 c = nxt.conv.cout
         super().__init__(net)
         self.supports_explain = True
-        self._train_plan = False                   # (bcos_hip/train_plan.py: no fused training plan; train() + autograd runs per layer)
+
+    @property
+    def train_plan_class(self):
+        """the plan `train_plan.train_forward` builds for net.train() + autograd (bcos_hip/densenet_train_plan.py)"""
+        from .densenet_train_plan import DenseNetTrainPlan
+        return DenseNetTrainPlan
 
     # ------------------------------------------------------------------------------------------------
     def _parts(self):

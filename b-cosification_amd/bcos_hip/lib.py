@@ -197,6 +197,11 @@ SIGNATURES = {
     "bcos_class_scores": (C.c_int, [_P, _P, _I, _I, _P, _L, _I, _P]),
     "bcos_slice_affine_rows": (C.c_int, [_P, _L, _P, _P, _P, _P, _L, _P, _L, _I, _I, _P]),
     "bcos_slice_affine_bwd_acc": (C.c_int, [_P, _P, _L, _P, _P, _P, _L, _L, _I, _I, _I, _P]),
+    "bcos_slice_col_ws_floats": (C.c_int, [_L, _I, C.POINTER(C.c_int64)]),
+    "bcos_slice_batch_stats": (C.c_int, [_P, _L, _P, _P, _P, _L, _L, _I, _P]),
+    "bcos_bn_reader_finish": (C.c_int, [_P, _P, _P, _P, _P, _I, _F, _F, _P]),
+    "bcos_slice_relu_bwd_colsums": (C.c_int, [_P, _P, _L, _P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _I, _P]),
+    "bcos_slice_bn_bwd_acc": (C.c_int, [_P, _P, _L, _P, _P, _P, _P, _P, _L, _L, _I, _I, _P]),
 }
 
 _lib = None

@@ -215,6 +215,31 @@ DEFAULT_TRACK_ABSMAX = True    # what tapconv(track_absmax=None) means while the
 F16X2_MIN_K = int(os.environ.get("BCOS_F16X2_MIN_K", "64"))     # below this K a launch keeps the bf16x3 loop (no operand maxima needed); same-node A/B on ResNet-50: 512 -> 256 = -0.4 ms per step (the K = 256 layers at 14^2 spend a third of their SIMD cycles on the 6 bf16 products); with the LDS-DMA loop of round 3 the K = 64 / 128 layers gain too (256 -> 128: -0.33 ms, -> 64: -0.39 ms per step)
 
 
+_CONTRACTION_OVERRIDE = None      # see contraction_override
+
+
+class contraction_override:
+    """Context: the contraction launches inside (tapconv and the grouped / boundary launches: forward and input-gradient contractions)
+    that are not given a `contraction=` of their own run in `mode` instead of the library default.  Everything else -- the ordered
+    weight gradient, which operand maxima are produced -- keeps following the default.  Used by the DenseNet training plan
+    (bcos_hip/densenet_train_plan.py: f32 products)."""
+
+    def __init__(self, mode: str):
+        if mode not in ("f32", "bf16x3", "f16x2"):
+            raise BcosHipError(f"contraction_override: unknown mode {mode!r}")
+        self.mode = mode
+
+    def __enter__(self):
+        global _CONTRACTION_OVERRIDE
+        self._prev = _CONTRACTION_OVERRIDE
+        _CONTRACTION_OVERRIDE = self.mode
+
+    def __exit__(self, *exc):
+        global _CONTRACTION_OVERRIDE
+        _CONTRACTION_OVERRIDE = self._prev
+        return False
+
+
 class no_absmax:
     """Context: launches inside do not emit per-pixel maxima unless asked to, so their readers keep the bf16x3 loop.  Used by
     plans whose contractions are too small-K for the f16x2 loop to pay (SimpleViT: K = 192 / 768 linears -- measured
@@ -401,7 +426,7 @@ def tapconv(a: torch.Tensor, wt: torch.Tensor, geom: dict, *, out=None, out2=Non
     e.addend_sub = int(addend_sub)
     if e.max_out > 1:                    # fused MaxOut: plain forward epilogue, no operand maxima of the (narrow) output
         track_absmax = track_absmax2 = False
-    mode = contraction if contraction is not None else _l.get_contraction_mode()
+    mode = contraction if contraction is not None else (_CONTRACTION_OVERRIDE or _l.get_contraction_mode())
     o = _l.Operands()
     o.a = _dev(a, "tapconv.a", contiguous=False).value
     o.wt = _dev(wt, "tapconv.wt").value
@@ -526,7 +551,7 @@ def boundary_conv3_grad(g1, w1t, addend, t3, w3t, t2, *, mul2=None, mul_norm=Non
     banks of conv1 above and conv3 below.  `track_absmax` / `track_absmax2`: the maxima of g3 / out2, as in tapconv.  BcosHipError with
     code BCOS_E_NOSUP for anything but this one configuration on the f16x2 contraction."""
     lib = _l.load()
-    mode = contraction if contraction is not None else _l.get_contraction_mode()
+    mode = contraction if contraction is not None else (_CONTRACTION_OVERRIDE or _l.get_contraction_mode())
     N, H, W, c1 = g1.shape
     c4 = addend.shape[-1]
     a = _l.BoundaryConv3()
@@ -1737,6 +1762,67 @@ def slice_affine_bwd_acc(d, g, x=None, scale=None, shift=None, relu=False, accum
     _l.check(lib.bcos_slice_affine_bwd_acc(_dev(d, "d"), _dev(x, "x", contiguous=False), xp, _dev(scale, "scale"), _dev(shift, "shift"),
                                            _dev(g, "g", contiguous=False), gp, rows, Cc, int(bool(relu)), int(bool(accumulate)), _stream()),
              "bcos_slice_affine_bwd_acc")
+    return g
+
+
+def _slice_col_ws(rows, Cc, device):
+    n = C.c_int64(0)
+    _l.check(_l.load().bcos_slice_col_ws_floats(rows, Cc, C.byref(n)), "bcos_slice_col_ws_floats")
+    return torch.empty((n.value,), device=device, dtype=torch.float32), n.value
+
+
+def slice_batch_stats(x, mean, var):
+    """mean[c], var[c] (centred second moment) of the channel slice `x` = X[..., lo:hi] over its rows, written into the [C] vectors (or
+    ranges of a block's shared vectors) `mean` / `var`; the summation order of a column depends on the row count alone
+    (include/bcos_hip.h: bcos_slice_batch_stats)."""
+    rows, Cc, xp = _row_slice(x, "slice_batch_stats.x")
+    if mean.numel() != Cc or var.numel() != Cc or not mean.is_contiguous() or not var.is_contiguous():
+        raise BcosHipError(f"slice_batch_stats: mean / var must be contiguous vectors of {Cc} floats")
+    ws, n = _slice_col_ws(rows, Cc, x.device)
+    _l.check(_l.load().bcos_slice_batch_stats(_dev(x, "x", contiguous=False), xp, _dev(mean, "mean"), _dev(var, "var"), _dev(ws, "workspace"), n,
+                                              rows, Cc, _stream()), "bcos_slice_batch_stats")
+    return mean, var
+
+
+def bn_reader_finish(var, weight, eps, running_var=None, momentum=0.0):
+    """-> (rstd, g = weight * rstd) of ONE reader of shared batch statistics, its running_var updated in place: one launch
+    (include/bcos_hip.h: bcos_bn_reader_finish)."""
+    Cc = var.numel()
+    rstd, g = (torch.empty((Cc,), device=var.device, dtype=torch.float32) for _ in range(2))
+    _l.check(_l.load().bcos_bn_reader_finish(_dev(var, "var"), _dev(weight, "weight"), _dev(running_var, "running_var"), _dev(rstd, "rstd"),
+                                             _dev(g, "g"), Cc, float(eps), float(momentum), _stream()), "bcos_bn_reader_finish")
+    if running_var is not None:          # written through its pointer: tell torch (plans keyed on tensor versions re-read it)
+        torch.autograd.graph.increment_version(running_var)
+    return rstd, g
+
+
+def slice_relu_bwd_colsums(d, x, gvec, shift=None, rstd=None, want_sg=False, want_gw=False, want_coef=False):
+    """-> (sgx, sg, gw, coef): the column sums of a training-mode pre-activation's backward pass from the dense gradient `d` and the raw
+    slice `x`, the ReLU gate rebuilt as the forward decided it (include/bcos_hip.h: bcos_slice_relu_bwd_colsums)."""
+    rows, Cc, xp = _row_slice(x, "slice_relu_bwd_colsums.x")
+    if d.numel() != rows * Cc or not d.is_contiguous():
+        raise BcosHipError("slice_relu_bwd_colsums: d must be a dense tensor of the slice's shape")
+    ws, n = _slice_col_ws(rows, Cc, x.device)
+    new = lambda: torch.empty((Cc,), device=x.device, dtype=torch.float32)      # noqa: E731
+    sgx, sg, gw, coef = new(), (new() if want_sg else None), (new() if want_gw else None), (new() if want_coef else None)
+    _l.check(_l.load().bcos_slice_relu_bwd_colsums(_dev(d, "d"), _dev(x, "x", contiguous=False), xp, _dev(gvec, "gvec"), _dev(shift, "shift"),
+                                                   _dev(rstd, "rstd"), _dev(sgx, "sgx"), _dev(sg, "sg"), _dev(gw, "gw"), _dev(coef, "coef"),
+                                                   _dev(ws, "workspace"), n, rows, Cc, _stream()), "bcos_slice_relu_bwd_colsums")
+    return sgx, sg, gw, coef
+
+
+def slice_bn_bwd_acc(d, g, x, scale=None, shift=None, mean=None, coef=None, accumulate=True):
+    """g (+)= gate d scale[c] + (x - mean[c]) coef[c] over the rows of the channel slice `g` = G[..., lo:hi]: the input gradient of a
+    training-mode pre-activation (include/bcos_hip.h: bcos_slice_bn_bwd_acc; `coef` None: the bits of slice_affine_bwd_acc)."""
+    rows, Cc, gp = _row_slice(g, "slice_bn_bwd_acc.g")
+    xrows, xc, xp = _row_slice(x, "slice_bn_bwd_acc.x")
+    if (xrows, xc) != (rows, Cc):
+        raise BcosHipError(f"slice_bn_bwd_acc: x holds {xrows} rows of {xc}, g {rows} rows of {Cc}")
+    if d.numel() != rows * Cc or not d.is_contiguous():
+        raise BcosHipError("slice_bn_bwd_acc: d must be a dense tensor of the slice's shape")
+    _l.check(_l.load().bcos_slice_bn_bwd_acc(_dev(d, "d"), _dev(x, "x", contiguous=False), xp, _dev(scale, "scale"), _dev(shift, "shift"),
+                                             _dev(mean, "mean"), _dev(coef, "coef"), _dev(g, "g", contiguous=False), gp, rows, Cc,
+                                             int(bool(accumulate)), _stream()), "bcos_slice_bn_bwd_acc")
     return g
 
 

@@ -20,7 +20,9 @@ Scope: torchvision-topology ResNets with the GAP + 1x1 `fc` head (BASELINE confi
 (CLIP/clip/model.py:10-154: three-convolution stem, anti-aliasing AvgPool2d between conv2 and conv3 and in front of the shortcut
 convolution; its attention-pool head runs as the module it is, under autograd, on the feature map the plan returns); groups == 1,
 max_out == 1, fixed B.  Anything else -- the `attn_unpool` head, grouped / MaxOut layers, a learnable exponent, native unit-norm
-layers -- is refused by `supported()` and keeps the per-layer path.
+layers -- is refused by `supported()` and keeps the per-layer path.  DenseNets (bcos_hip/densenet_engine.py) train through
+DenseNetTrainPlan (bcos_hip/densenet_train_plan.py), which reuses the convolution units below and adds the pre-activation norms over
+channel slices; `train_forward` picks the plan class the attached engine names (`train_plan_class`).
 """
 import contextlib
 import os
@@ -458,8 +460,9 @@ def train_forward(eng, x: torch.Tensor) -> Optional[torch.Tensor]:
     """`net(x)` in train() mode through the plan, or None when the network is outside the plan's scope (per-layer path then)."""
     plan = getattr(eng, "_train_plan", None)
     if plan is None:
-        ok, _ = ResNetTrainPlan.supported(eng)
-        plan = ResNetTrainPlan(eng) if ok else False
+        cls = getattr(eng, "train_plan_class", ResNetTrainPlan)          # (an engine of another topology names its own plan)
+        ok, _ = cls.supported(eng)
+        plan = cls(eng) if ok else False
         eng._train_plan = plan
     if plan is False:
         return None

@@ -649,6 +649,66 @@ int bcos_slice_affine_rows(const float* x, int64_t x_pitch, const float* scale, 
 int bcos_slice_affine_bwd_acc(const float* d, const float* x, int64_t x_pitch, const float* scale, const float* shift, float* g,
                               int64_t g_pitch, int64_t rows, int C, int relu, int accumulate, void* stream);
 
+/* -- the same consumers in TRAINING mode (bcos_dense.hip; additive entry points of ABI v12, recognised by symbol presence) ----------
+ * BatchNormUncentered2d with batch statistics (reference bcos/modules/norms/uncentered_norms/batchnorm_uncentered.py:36-44) as torchvision's
+ * _DenseLayer.norm1, _Transition.norm and norm5 apply it to cat(features): var = x.var((0, 2, 3), unbiased=False) -- the centred second
+ * moment although nothing is centred --, running_var <- (1 - momentum) running_var + momentum var, y = x weight / sqrt(var + eps) + bias.
+ * Every reader of a channel of the concatenation sees the same column, so (mean, var) of a channel are computed ONCE, when its slice of
+ * the block buffer is complete, and shared; a reader adds its own weight / eps / momentum / running_var (bcos_bn_reader_finish).
+ * Throughout, x is a slice [rows, C] of pitched rows, C % 4 == 0, a pitch of 0 means C; nothing outside [0, C) of a pitched row is read
+ * or written; nothing uses atomics.
+ *
+ * The column reductions (bcos_slice_batch_stats, bcos_slice_relu_bwd_colsums) split the rows into nblk blocks of rpb rows,
+ *     nblk0 = min(ceil(rows / 128), 1024), rpb = ceil(rows / nblk0), nblk = ceil(rows / rpb)
+ * -- a function of `rows` alone --, and take a caller-owned workspace of bcos_slice_col_ws_floats(rows, C) = 3 nblk C floats (16-byte
+ * aligned).  Inside a block a column's rows r_lo + t, r_lo + t + 32, ... are added in order by lane t < 32, the 32 lanes in lane order,
+ * the blocks in block order by a second launch: the summation order of a column depends on `rows` alone, NOT on C, the pitch, the slice
+ * offset or which other columns are in the call.  The results of a 96-channel slice are bit for bit those of three calls of 32 channels.
+ * No addend passes through more than D(rows) = ceil(rpb / 32) + ceil(nblk / 16) + 56 additions.
+ *
+ * bcos_slice_batch_stats: ONE pass over x.  mean[c], var[c] = the centred second moment, from per-block sums of (x - c_b) and (x - c_b)^2
+ * shifted by the block's first row c_b and combined as (n_b, mean_b, M2_b) (Chan et al.).  With A = max_r |x[r, c]| and
+ * R = max_r |x[r, c] - mean[c]| (exact mean):   |mean - exact| <= 2^-23 * 3 D A,   |var - exact| <= 2^-23 * D (16 R^2 + 2 R A).
+ * BCOS_E_INVAL: NULL x / mean / var / workspace, rows <= 0, C <= 0, C % 4 != 0, a nonzero pitch < C or not a multiple of 4, x or the
+ * workspace not 16-byte aligned (mean, var: 4-byte), a workspace smaller than the query's.  BCOS_E_NOSUP: C > 2097120. */
+int bcos_slice_col_ws_floats(int64_t rows, int C, int64_t* floats);
+int bcos_slice_batch_stats(const float* x, int64_t x_pitch, float* mean, float* var, float* workspace, int64_t workspace_floats,
+                           int64_t rows, int C, void* stream);
+
+/* One reader's share, ONE launch on [C] vectors: rstd = 1 / sqrt(var + eps), g = weight * rstd (weight NULL: rstd) and -- running_var not
+ * NULL -- running_var = (1 - momentum) running_var + momentum var in place.  var is the reader's range of a block's shared vector.
+ * |rstd - exact| <= 2^-22 exact (the sum's rounding and rsqrtf's), |g - weight exact rstd| <= 3 * 2^-23 |g|,
+ * |running_var - exact| <= 2^-22 ((1 - momentum) |running_var_old| + momentum |var|).
+ * BCOS_E_INVAL: NULL var / rstd / g, C <= 0, eps < 0, momentum outside [0, 1], a vector that is not 4-byte aligned. */
+int bcos_bn_reader_finish(const float* var, const float* weight, float* running_var, float* rstd, float* g, int C, float eps, float momentum,
+                          void* stream);
+
+/* The column sums of that norm's backward pass from the dense incoming gradient d [rows, C] (w.r.t. the OUTPUT of norm + ReLU) and the raw
+ * slice x, without writing a per-element tensor:   sgx[c] = sum_r gate d x,   sg[c] = sum_r gate d (sg may be NULL),
+ * gate = (x * gvec[c] + shift[c] > 0) with the two roundings of bcos_slice_affine_rows (shift may be NULL), so gate <=> (the forward's
+ * y > 0) bit for bit.  Its finish also writes gw = sgx * rstd (the norm's weight gradient; may be NULL) and
+ * coef = -(gvec * sgx) * rstd^2 / rows (the variance-term coefficient of bcos_slice_bn_bwd_acc; may be NULL) -- the formulas of
+ * bcos_relu_bwd_colsums.  Order and workspace as above (2 nblk C floats are used):
+ *     |sgx - exact| <= 2^-23 D sum_r |gate d x|,   |sg - exact| <= 2^-23 D sum_r |gate d|;
+ * gw is one rounding from sgx * rstd, coef four from its formula (|coef - formula(sgx)| <= 5 * 2^-24 |coef|).
+ * BCOS_E_INVAL: NULL d / x / gvec / sgx / workspace, gw or coef without rstd, rows / C / pitch as above, d / x / gvec / shift / workspace
+ * not 16-byte aligned (the other vectors: 4-byte), a workspace smaller than the query's.  BCOS_E_NOSUP as above. */
+int bcos_slice_relu_bwd_colsums(const float* d, const float* x, int64_t x_pitch, const float* gvec, const float* shift, const float* rstd,
+                                float* sgx, float* sg, float* gw, float* coef, float* workspace, int64_t workspace_floats, int64_t rows,
+                                int C, void* stream);
+
+/* The training form of bcos_slice_affine_bwd_acc (relu = 1): the norm's input gradient added into the reader's slice of the block's
+ * gradient buffer,
+ *     g[r * g_pitch + c] = (accumulate ? g[r * g_pitch + c] : 0) + gate * d[r * C + c] * scale[c] + (x[r * x_pitch + c] - mean[c]) * coef[c],
+ * gate as above, scale = weight / std, coef from bcos_slice_relu_bwd_colsums.  coef NULL (then mean must be NULL too): the variance is a
+ * constant -- a norm in eval() inside net.train(), or `detach` -- and the call writes the bits of bcos_slice_affine_bwd_acc; mean NULL
+ * with coef: 0.  Roundings in this order: d scale; x - mean; (.) coef; their sum; the sum with the old g.  Per element
+ *     |g - exact| <= 2^-23 (|g_old| + 2 |d scale| + 2 |(x - mean) coef|)      (coef NULL: 2^-23 (|g_old| + |d scale|), as there).
+ * accumulate = 0 never reads g.  BCOS_E_INVAL: NULL d / x / g, mean without coef, rows / C / pitches / alignment (every tensor 16-byte) /
+ * accumulate as for bcos_slice_affine_bwd_acc.  BCOS_E_NOSUP: C > 8192 with C / 4 not a divisor of 64. */
+int bcos_slice_bn_bwd_acc(const float* d, const float* x, int64_t x_pitch, const float* scale, const float* shift, const float* mean,
+                          const float* coef, float* g, int64_t g_pitch, int64_t rows, int C, int accumulate, void* stream);
+
 /* -- training-mode backward (bcos_train.hip) ------------------------------------------ */
 /* Outside explanation mode the dynamic scale is not detached (bcosconv2d.py:176-194), so with lin = conv(x, W) (+ bias),
  * y = s(lin, norm) * lin:   gx = dgrad(gy * dy/dlin, W) + x (.) PatchSum^T(dL/dnorm / norm),   gW = wgrad(gy * dy/dlin, x).

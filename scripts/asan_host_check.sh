@@ -1,7 +1,7 @@
 #!/bin/bash
 # AddressSanitizer check of the C ABI's host side (no GPU needed): builds libbcos_hip with the HOST code sanitised
 # (device code unsanitised: -fno-gpu-sanitize; GPU ASan is unavailable on the pool) and runs tests/asan/abi_validation.c,
-# tests/asan/agc_abi_validation.c, tests/asan/occlusion_abi_validation.c, tests/asan/rise_abi_validation.c, tests/asan/head_functional_abi_validation.c, tests/asan/boundary_abi_validation.c, tests/asan/perturbation_abi_validation.c and tests/asan/dense_abi_validation.c against it.  Usage: scripts/asan_host_check.sh   (exit code 0 = clean)
+# tests/asan/agc_abi_validation.c, tests/asan/occlusion_abi_validation.c, tests/asan/rise_abi_validation.c, tests/asan/head_functional_abi_validation.c, tests/asan/boundary_abi_validation.c, tests/asan/perturbation_abi_validation.c, tests/asan/dense_abi_validation.c and tests/asan/dense_train_abi_validation.c against it.  Usage: scripts/asan_host_check.sh   (exit code 0 = clean)
 # The objects are compiled in parallel, bcos_tapconv.hip in the same -DBCOS_TAPCONV_PART slices as the product build.
 set -e
 ROOT="$(cd "$(dirname "$0")/.." && pwd)"
@@ -26,7 +26,7 @@ if [ ! -f "$LIB" ] || [ "$newest" -nt "$LIB" ]; then
   printf '%s\n' "${jobs[@]}" | xargs -P 8 -I{} bash -c "{}"
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -fsanitize=address -fno-gpu-sanitize "$OUT"/obj/*.o -o "$LIB"
 fi
-for t in abi_validation agc_abi_validation occlusion_abi_validation rise_abi_validation head_functional_abi_validation boundary_abi_validation perturbation_abi_validation dense_abi_validation; do
+for t in abi_validation agc_abi_validation occlusion_abi_validation rise_abi_validation head_functional_abi_validation boundary_abi_validation perturbation_abi_validation dense_abi_validation dense_train_abi_validation; do
   /opt/rocm/lib/llvm/bin/clang -O1 -g -fsanitize=address -fno-gpu-sanitize -fno-omit-frame-pointer -I"$ROOT/include" \
      "$ROOT/tests/asan/$t.c" -L"$OUT" -lbcos_hip_asan -lm -Wl,-rpath,"$OUT" -o "$OUT/$t"
   ASAN_OPTIONS=detect_leaks=0:abort_on_error=0 "$OUT/$t"
