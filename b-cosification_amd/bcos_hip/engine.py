@@ -59,6 +59,36 @@ def set_boundary_fusion(on):
     return old
 
 
+# The 1 x 1 downsample shortcut of a stage's first bottleneck and the conv3 beside it as ONE forward launch (ops.shortcut_conv3_fwd: the
+# [N, P, Q, 4C] shortcut output never reaches memory; same bits).  BCOS_SHORTCUT_FUSION=0: the pair of launches, for A/B runs;
+# set_shortcut_fusion() flips it inside a process.  SHORTCUT_FUSION_CALLS counts the fused launches issued.
+_SHORTCUT_FUSION_ENV = os.environ.get("BCOS_SHORTCUT_FUSION", "1") != "0"
+_SHORTCUT_FUSION = _SHORTCUT_FUSION_ENV
+SHORTCUT_FUSION_CALLS = 0
+
+
+def set_shortcut_fusion(on):
+    """True / False: the fused shortcut launch on / off; None: back to what BCOS_SHORTCUT_FUSION says.  Returns the previous setting."""
+    global _SHORTCUT_FUSION
+    old, _SHORTCUT_FUSION = _SHORTCUT_FUSION, (_SHORTCUT_FUSION_ENV if on is None else bool(on))
+    return old
+
+
+class _DeferredShortcut:
+    """What Conv.fwd(..., defer=True) of a shortcut convolution returns in place of its output: the launch is left to the conv3 call that
+    is handed this record as its `addend` (one fused launch, or -- where that call is refused -- the pair of launches after all).
+    `.shape` is the NHWC shape of the output the shortcut would have written; `.td` receives its multiplier."""
+
+    def __init__(self, conv, x, want_scale):
+        self.conv, self.x, self.want_scale, self.td = conv, x, want_scale, None
+        self.shape = (x.shape[0],) + conv.out_hw(x.shape[1], x.shape[2]) + (conv.cout,)
+
+    def run(self):
+        """the shortcut's own launch -> its output"""
+        y, self.td = self.conv.fwd(self.x, relu=False, want_scale=self.want_scale, track=False)
+        return y
+
+
 def _pair(v):
     return (v, v) if isinstance(v, int) else (int(v[0]), int(v[1]))
 
@@ -145,11 +175,29 @@ class Conv:
         """largest K of the input-gradient launches (their A operand is the gradient w.r.t. this layer's `lin`)."""
         return (self.cout_all // self.groups) * self.k[0] * self.k[1]
 
-    def fwd(self, x, *, addend=None, relu=False, want_scale=False, gates=None, flags=0, track=None, keep_act=False):
+    def fwd(self, x, *, addend=None, relu=False, want_scale=False, gates=None, flags=0, track=None, keep_act=False, defer=False):
         """-> (y, t).  `keep_act` (explanation state of a layer whose output stays alive anyway is cheaper to REBUILD than to
         store): when the layer allows it -- B = 2, plain |lin| / norm scale, own ReLU decided by the value, no residual -- t
         is not written; the returned `t` is then an _ActScale record (activation, patch norms, BN scale / shift) from which
         the consuming input-gradient launch rebuilds the multiplier (BCOS_EPI_MUL_FROM_ACT)."""
+        if defer:        # a fusable shortcut convolution (see _shortcut_fusable): launched by the conv3 call that takes the record as its addend
+            return _DeferredShortcut(self, x, want_scale), None
+        if isinstance(addend, _DeferredShortcut):
+            global SHORTCUT_FUSION_CALLS
+            sc = addend
+            try:
+                out, t, sc.td = ops.shortcut_conv3_fwd(sc.x, sc.conv.w_fwd, x, self.w_fwd, stride=sc.conv.stride[0], csc_d=sc.conv.ch_scale,
+                                                       csh_d=sc.conv.ch_shift, csc_3=self.ch_scale, csh_3=self.ch_shift, want_scale=want_scale,
+                                                       flags=flags, track_absmax=track, b=self.b, bias_d=sc.conv.bias, bias_3=self.bias)
+                SHORTCUT_FUSION_CALLS += 1
+                self.last_gate = None
+                return out, t
+            except BcosHipError as err:
+                # (what _shortcut_fusable cannot see from where it stands, e.g. a misaligned view: the call refuses before it launches
+                #  anything, and the pair of launches takes the site as it always did)
+                if err.code != BCOS_E_NOSUP:
+                    raise
+                addend = sc.run()
         gate = gates.pop(0) if (relu and gates is not None) else None
         if self.max_out > 1:
             return self._fwd_maxout(x, addend, relu, want_scale, gate, flags, track)
@@ -494,7 +542,9 @@ class ResNetEngine(FusedPlan):
             if blk.shortcut is not None:
                 sc_in = (ops.avgpool2d_fwd(inp, blk.shortcut_pool, blk.shortcut_pool, 0, want_absmax=need(blk.shortcut.k_fwd))
                          if blk.shortcut_pool else inp)
-                idn, td = blk.shortcut.fwd(sc_in, relu=False, want_scale=keep, track=False)      # only ever an addend
+                # (a fusable site: the call defers, conv3's call below issues the one launch for both and fills in td)
+                idn, td = blk.shortcut.fwd(sc_in, relu=False, want_scale=keep, track=False,      # only ever an addend
+                                           defer=_shortcut_fusable(blk, sc_in, h, gates))
             else:
                 idn, td = inp, None
             hws.append((h.shape[1], h.shape[2]))
@@ -506,6 +556,8 @@ class ResNetEngine(FusedPlan):
                 k_next = self.head.k_fwd if self.head is not None else ops.F16X2_MIN_K
             out, t = blk.convs[-1].fwd(h, addend=idn, relu=blk.relu, want_scale=keep, gates=gates, track=need(k_next),
                                        flags=BCOS_EPI_SCALE_GATE_LSB if (keep and blk.relu and not _GATE_TENSOR) else 0)
+            if isinstance(idn, _DeferredShortcut):
+                td = idn.td
             ts.append(t)
             tw.append(blk.convs[-1].take_wide())
             if keep:
@@ -775,6 +827,41 @@ class ResNetEngine(FusedPlan):
                                                 weights_out=outs[0] if outs is not None else None,
                                                 contrib_out=outs[1] if outs is not None else None)
         return wts, contrib
+
+
+# (K3, Kd, stride, C4) of the sites the engine hands to the fused shortcut launch.  The call also takes (128, 256, 2, 512), layer2.0 of a
+# ResNet-50 (include/bcos_hip.h: bcos_shortcut_conv3_fwd), but at batch 256 that site measured SLOWER fused than as the pair of launches
+# (634 against 568 us: 48 dependent 16-k steps per workgroup with the weight fragments straight out of L2; profiles/shortcut_fusion_ab.txt),
+# so it stays on the pair; layer1.0 gains (661 against 926 us).
+_SHORTCUT_CONFIGS = ((64, 64, 1, 256),)
+
+
+def _shortcut_fusable(blk, sc_in, h, gates) -> bool:
+    """May ops.shortcut_conv3_fwd stand in for the forward launches of blk's shortcut convolution and of its last convolution?  Both are
+    plain 1 x 1 layers (B = 2, no MaxOut, no groups, no bias) of one of the supported width / stride configurations, no anti-aliasing pool
+    in front of either (CLIP), a ReLU decided by the value (no replayed gates, no separate gate tensor), f16x2 contraction with the maxima
+    of both inputs at hand and both weight banks with their pre-split images, contiguous tensors below the 2 GiB of the kernel's 32-bit
+    offsets.  On a device the native call; on CPU tensors only where a test has put an emulator in the call's place.  (The call's own
+    refusals are mirrored here; one that is met anyway -- BCOS_E_NOSUP -- sends the site to the pair of launches too.)"""
+    if not _SHORTCUT_FUSION or blk.shortcut is None or len(blk.convs) < 3 or gates is not None or _GATE_TENSOR:
+        return False
+    cd, c3 = blk.shortcut, blk.convs[-1]
+    if not (h.is_cuda or not getattr(ops.shortcut_conv3_fwd, "native", False)):
+        return False
+    plain = lambda c: (c.k == (1, 1) and c.padding == (0, 0) and c.dilation == (1, 1) and c.max_out == 1 and c.groups == 1       # noqa: E731
+                       and c.b == 2.0 and not c.force_pow and c.bias is None and c.w_fwd.shape[3] == c.cin)
+    N, P, Q = h.shape[0], h.shape[1], h.shape[2]
+    am_x, am_h = ops.absmax_of(sc_in), ops.absmax_of(h)
+    return bool(plain(cd) and plain(c3) and blk.relu and not blk.pool and not blk.shortcut_pool
+                and cd.stride[0] == cd.stride[1] and c3.stride == (1, 1) and cd.cout == c3.cout
+                and (c3.cin, cd.cin, cd.stride[0], c3.cout) in _SHORTCUT_CONFIGS
+                and tuple(cd.out_hw(sc_in.shape[1], sc_in.shape[2])) == (P, Q) and sc_in.shape[0] == N
+                and sc_in.is_contiguous() and h.is_contiguous()
+                and N * P * Q * c3.cout * 4 < 2 ** 31 and sc_in.numel() * 4 < 2 ** 31
+                and ops.presplit_static(cd.w_fwd) and ops.presplit_static(c3.w_fwd)
+                and _l_mode() == "f16x2" and ops.F16X2_MIN_K <= min(c3.cin, cd.cin)
+                and am_x is not None and am_x.numel() == sc_in.numel() // sc_in.shape[3]
+                and am_h is not None and am_h.numel() == N * P * Q)
 
 
 def _boundary_fusable(consumer, blk, rec, H, W) -> bool:

@@ -19,7 +19,7 @@ LIB_PATH = Path(os.environ["BCOS_HIP_LIB"]) if os.environ.get("BCOS_HIP_LIB") el
 CSRC = PKG_ROOT / "csrc"
 INCLUDE = REPO_ROOT / "include"
 SOURCES = ["bcos_tapconv.hip", "bcos_skinny.hip", "bcos_elementwise.hip", "bcos_vit.hip", "bcos_render.hip", "bcos_train.hip",
-           "bcos_agc.hip", "bcos_occlusion.hip", "bcos_rise.hip", "bcos_perturb.hip", "bcos_head.hip", "bcos_boundary.hip", "bcos_dense.hip", "bcos_abi.hip"]
+           "bcos_agc.hip", "bcos_occlusion.hip", "bcos_rise.hip", "bcos_perturb.hip", "bcos_head.hip", "bcos_boundary.hip", "bcos_shortcut.hip", "bcos_dense.hip", "bcos_abi.hip"]
 
 BCOS_NONE, BCOS_CONV_EPS, BCOS_LINEAR_EPS = 0, 1, 2
 BCOS_EPI_NORM_ONLY = 1
@@ -85,6 +85,14 @@ class BoundaryConv3(C.Structure):
         "g1", "g1_absmax", "w1_f16x2", "addend", "t3", "mul2", "out2", "out2_absmax", "w3_f16x2", "t2", "mul_norm", "mul_csc", "mul_csh",
         "g3", "g3_absmax", "g3_imgmax", "g3_imgmin_c")] + [(n, C.c_int32) for n in (
         "N", "PQ", "C1", "C4", "kh", "kw", "stride", "contraction")] + [("b", C.c_float)]
+
+
+class ShortcutConv3(C.Structure):
+    """include/bcos_hip.h: bcos_shortcut_conv3"""
+    _fields_ = [(n, C.c_void_p) for n in (
+        "x", "x_absmax", "wd_f16x2", "csc_d", "csh_d", "td", "h", "h_absmax", "w3_f16x2", "csc_3", "csh_3", "out", "t3", "out_absmax",
+        "bias_d", "bias_3", "relu_gate")] + [(n, C.c_int32) for n in (
+        "N", "H", "W", "K3", "Kd", "C4", "kh", "kw", "stride", "max_out", "groups", "contraction", "flags")] + [("b", C.c_float)]
 
 
 LOOP_NAMES = ("f32", "bf16x3", "bf16x3_presplit", "f16x2_regs", "f16x2_dma", "f16x2_patch")      # include/bcos_hip.h: BCOS_LOOP_*
@@ -191,6 +199,7 @@ SIGNATURES = {
     "bcos_prep_input_rise": (C.c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "bcos_rise_accumulate": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P]),
     "bcos_boundary_conv3_grad": (C.c_int, [C.POINTER(BoundaryConv3), _P]),
+    "bcos_shortcut_conv3_fwd": (C.c_int, [C.POINTER(ShortcutConv3), _P]),
     "bcos_perturb_select_ws_bytes": (C.c_int, [_I, _L, _I, C.POINTER(C.c_int64)]),
     "bcos_perturb_select": (C.c_int, [_P, _P, _I, _P, _P, _L, _I, _L, _I, _P]),
     "bcos_prep_input_perturbed": (C.c_int, [_P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),

@@ -609,6 +609,70 @@ def boundary_conv3_grad(g1, w1t, addend, t3, w3t, t2, *, mul2=None, mul_norm=Non
     return g3, out2
 
 
+def shortcut_conv3_fwd(x, wd, h, w3, *, stride=1, csc_d=None, csh_d=None, csc_3=None, csh_3=None, want_scale=False, flags=0,
+                       track_absmax=None, b=2.0, bias_d=None, bias_3=None, relu_gate=None, max_out=1, groups=1, contraction=None):
+    """The 1 x 1 downsample shortcut of a stage's first bottleneck and the conv3 beside it in ONE forward launch
+    (include/bcos_hip.h: bcos_shortcut_conv3_fwd) -> (out [N,P,Q,C4], t3, td), bit for bit what
+        conv2d_fwd(x, wd, stride=stride, ch_scale=csc_d, ch_shift=csh_d, want_scale=want_scale, track_absmax=False)  -> idn, td  and
+        conv2d_fwd(h, w3, ch_scale=csc_3, ch_shift=csh_3, addend=idn, relu=True, want_scale=want_scale, flags=flags) -> out, t3
+    give, without idn.  x [N,H,W,Kd] (the block input) and h [N,P,Q,K3] (conv2's output) carry their per-pixel maxima; wd [C4,1,1,Kd] /
+    w3 [C4,1,1,K3] are the (static) forward banks.  t3 / td are None unless `want_scale`; `track_absmax`: the maxima of out, as in
+    tapconv.  BcosHipError with code BCOS_E_NOSUP for anything but the supported configurations on the f16x2 contraction."""
+    lib = _l.load()
+    mode = contraction if contraction is not None else (_CONTRACTION_OVERRIDE or _l.get_contraction_mode())
+    N, H, W, kd = x.shape
+    k3 = h.shape[-1]
+    c4 = wd.shape[0]
+    s = int(stride)
+    P, Q = (H + s - 1) // s, (W + s - 1) // s
+    am_x, am_h = absmax_of(x), absmax_of(h)
+    static = presplit_static(wd) and presplit_static(w3)
+    if (mode != "f16x2" or am_x is None or am_x.numel() != N * H * W or am_h is None or am_h.numel() != N * P * Q or not static
+            or tuple(wd.shape) != (c4, 1, 1, kd) or tuple(w3.shape) != (c4, 1, 1, k3) or tuple(h.shape) != (N, P, Q, k3)
+            or min(kd, k3) < F16X2_MIN_K or any(t is not None and tuple(t.shape) != (c4,) for t in (csc_d, csh_d, csc_3, csh_3))):
+        err = BcosHipError("shortcut_conv3_fwd: needs the f16x2 contraction, the per-pixel maxima of x and h, static 1 x 1 weight banks "
+                           "[C4,1,1,Kd] / [C4,1,1,K3] and tensors of the matching shapes")
+        err.code = _l.BCOS_E_NOSUP
+        raise err
+    a = _l.ShortcutConv3()
+    a.N, a.H, a.W, a.K3, a.Kd, a.C4, a.kh, a.kw, a.stride = N, H, W, k3, kd, c4, 1, 1, s
+    a.max_out, a.groups, a.flags, a.b = int(max_out), int(groups), int(flags), float(b)
+    a.contraction = {"f32": _l.CONTRACT_F32, "bf16x3": _l.CONTRACT_BF16X3, "f16x2": _l.CONTRACT_F16X2}[mode]
+    out = torch.empty((N, P, Q, c4), device=x.device, dtype=torch.float32)
+    t3 = torch.empty_like(out) if want_scale else None
+    td = torch.empty_like(out) if want_scale else None
+    tensors = dict(x=x, csc_d=csc_d, csh_d=csh_d, td=td, h=h, csc_3=csc_3, csh_3=csh_3, out=out, t3=t3, bias_d=bias_d, bias_3=bias_3,
+                   relu_gate=relu_gate)
+    for k, t in tensors.items():
+        p = _dev(t, f"shortcut_conv3_fwd.{k}")
+        setattr(a, k, p.value if p is not None else None)
+    a.x_absmax, a.h_absmax = am_x.data_ptr(), am_h.data_ptr()
+    a.wd_f16x2 = _image_of(wd, "_bcos_wt2_t1", lambda w: split_weights_f16x2(w, 1)).data_ptr()
+    a.w3_f16x2 = _image_of(w3, "_bcos_wt2_t1", lambda w: split_weights_f16x2(w, 1)).data_ptr()
+    pixels = N * P * Q
+    am = _out_absmax(out, pixels) if (DEFAULT_TRACK_ABSMAX if track_absmax is None else track_absmax) else None
+    if am is not None:
+        a.out_absmax = am.data_ptr()
+    timing = KERNEL_TIMING
+    if timing is not None:
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        ev0.record()
+    code = lib.bcos_shortcut_conv3_fwd(C.byref(a), _stream())
+    if timing is not None:
+        ev1.record()
+        # one record per CONTRACTION of a step (see boundary_conv3_grad): time, flops and algorithmic bytes on the first, a zero-length
+        # marker for the second (it names the contraction it stands for, conv3's [pixels, K3] x [K3, C4]; no time, flops or bytes).
+        # Bytes as tapconv counts them: both A operands and both banks once, every output-sized tensor once.
+        nbytes = int(4 * (N * H * W * kd + pixels * k3 + (kd + k3) * c4 + pixels * c4 * (3 if want_scale else 1)))
+        timing.append((ev0, ev1, 2.0 * pixels * (kd + k3) * c4, nbytes, (pixels, kd + k3, c4)))
+        timing.append((ev1, ev1, 0.0, 0, (pixels, k3, c4)))
+    _l.check(code, "bcos_shortcut_conv3_fwd")
+    return out, t3, td
+
+
+shortcut_conv3_fwd.native = True       # (the engines take the fused route on CPU tensors only where a test has put an emulator in its place)
+
+
 def fwd_geom(N, H, W, Cin, Cout, kh, kw, sh, sw, ph, pw, dh=1, dw=1):
     Ho, Wo = conv_out_size(H, kh, sh, ph, dh), conv_out_size(W, kw, sw, pw, dw)
     return dict(N=N, H=H, W=W, C=Cin, P=Ho, Q=Wo, in_sh=sh, in_sw=sw, dh0=-ph, dw0=-pw, dstep_h=dh,

@@ -1085,6 +1085,52 @@ typedef struct bcos_boundary_conv3 {
 } bcos_boundary_conv3;
 int bcos_boundary_conv3_grad(const bcos_boundary_conv3* args, void* stream);
 
+/* -- downsample shortcut fused into conv3's forward launch (additive entry point of ABI v12) --------------------------------- */
+/* For the first bottleneck of a stage (a 1 x 1 shortcut convolution beside the 1 x 1 conv3 whose epilogue adds it; M = N * P * Q output
+ * pixels) ONE launch computes what two bcos_tapconv_ops forward launches compute -- the shortcut convolution (B-cos scale, channel affine,
+ * no ReLU; optionally its multiplier), then conv3 with that launch's `out` as its addend, ReLU and optionally its multiplier -- without the
+ * shortcut's output ever reaching memory:
+ *     idn = csc_d (lin_d s_d) + csh_d           lin_d = x_sub Wd^T [M,Kd] x [Kd,C4], x_sub = pixels (p stride, q stride) of x [N,H,W,Kd],
+ *     td  = s_d csc_d                           s = |lin| / sqrt(sum_k a_k^2 + 1e-6) of the row (BCOS_CONV_EPS, B = 2); td NULL or [M,C4]
+ *     y   = csc_3 (lin_3 s_3) + csh_3 + idn     lin_3 = h W3^T [M,K3] x [K3,C4]
+ *     out = relu(y);  t3 = s_3 csc_3 where y > 0, else 0 (NULL or [M,C4]); with BCOS_EPI_SCALE_GATE_LSB in `flags` an open gate also sets
+ *                                               the low mantissa bit of t3
+ * on the f16x2 contraction, bit for bit what the two launches give: out, t3, td and out_absmax (NULL or [M]).  P = ceil(H / stride),
+ * Q = ceil(W / stride).  wd_f16x2 / w3_f16x2: the images bcos_split_weights_f16x2 makes of the shortcut weights [C4][Kd] and of the conv3
+ * weights [C4][K3]; csc_* / csh_* (NULL = 1 / 0): the folded BatchNorm of the two layers, [C4] each.  Nothing is allocated and no device
+ * memory is read by the host.
+ * BCOS_E_INVAL: a NULL x / h / out, N / H / W <= 0, td without t3 or t3 without td, flag bits other than BCOS_EPI_SCALE_GATE_LSB.  BCOS_E_NOSUP: anything but
+ * (K3, Kd, stride, C4) = (64, 64, 1, 256) or (128, 256, 2, 512), 1 x 1 kernels (kh = kw = 1), b = 2, max_out = 1, groups = 1, no bias, no
+ * replayed gate tensor, contraction BCOS_CONTRACT_F16X2 (or the default while the process-wide mode is f16x2) with both images and both
+ * operands' maxima, tensors below 2 GiB and 16-byte aligned pointers (4-byte for the maxima arrays). */
+typedef struct bcos_shortcut_conv3 {
+    const float* x;              /* [N,H,W,Kd]: the block input               */
+    const uint32_t* x_absmax;    /* [N*H*W]: its per-pixel maxima             */
+    const void* wd_f16x2;
+    const float* csc_d;          /* NULL or [C4] */
+    const float* csh_d;          /* NULL or [C4] */
+    float* td;                   /* NULL or [M,C4] */
+    const float* h;              /* [M,K3]: conv2's output                    */
+    const uint32_t* h_absmax;    /* [M] */
+    const void* w3_f16x2;
+    const float* csc_3;          /* NULL or [C4] */
+    const float* csh_3;          /* NULL or [C4] */
+    float* out;                  /* [M,C4] */
+    float* t3;                   /* NULL or [M,C4] */
+    uint32_t* out_absmax;        /* NULL or [M] */
+    const float* bias_d;         /* must be NULL (BCOS_E_NOSUP) */
+    const float* bias_3;         /* must be NULL (BCOS_E_NOSUP) */
+    const float* relu_gate;      /* must be NULL (BCOS_E_NOSUP): replayed gates keep the pair of launches */
+    int32_t N, H, W;             /* the block input's extent */
+    int32_t K3, Kd, C4;
+    int32_t kh, kw, stride;      /* kernel of both convolutions, stride of the shortcut */
+    int32_t max_out, groups;
+    int32_t contraction;         /* BCOS_CONTRACT_* */
+    int32_t flags;               /* 0 or BCOS_EPI_SCALE_GATE_LSB */
+    float b;                     /* the B-cos exponent of the layers */
+} bcos_shortcut_conv3;
+int bcos_shortcut_conv3_fwd(const bcos_shortcut_conv3* args, void* stream);
+
 /* -- pixel perturbation (deletion curves; additive entry points of ABI v12) ------------------------------------------------- */
 /* An image's HW = H * W pixels are ranked by a score s (fp32, one per pixel p = h * W + w) and the first k of the ranking are REMOVED:
  * all six channels of the [r,g,b,1-r,1-g,1-b] network input are set to 0 there, as inside an Occlusion rectangle.  THE RANKING, stated
