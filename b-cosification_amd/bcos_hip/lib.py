@@ -28,6 +28,7 @@ BCOS_EPI_SCALE_GATE_LSB = 4
 BCOS_EPI_GATE2_FROM_MUL = 8
 BCOS_EPI_MUL_FROM_ACT = 16
 BCOS_EPI_UNIT_NORM_W = 32
+BCOS_E_INVAL = -22
 BCOS_E_NOSUP = -95
 ABI_VERSION = 12
 VERSION_DEV_FLAG = 0x40000000          # include/bcos_hip.h: BCOS_VERSION_DEV_FLAG
@@ -77,6 +78,12 @@ class AgcTensor(C.Structure):
 class TapconvRoute(C.Structure):
     """include/bcos_hip.h: bcos_tapconv_route"""
     _fields_ = [(n, C.c_int32) for n in ("route", "epi_kind", "norm", "loop", "bm", "bn", "chunks", "ch_pass")]
+
+
+class WgradPlan(C.Structure):
+    """include/bcos_hip.h: bcos_wgrad_plan"""
+    _fields_ = [(n, C.c_int32) for n in ("fused_taps", "direct", "tiles_co", "tiles_ci", "grid_y", "split", "combine", "reserved")] + [
+        (n, C.c_int64) for n in ("chunk", "last", "ws_floats")]
 
 
 class BoundaryConv3(C.Structure):
@@ -139,6 +146,7 @@ SIGNATURES = {
     "bcos_conv2d_wgrad": (C.c_int, [_P, _P, _P] + [_I] * 18 + [_P]),
     "bcos_conv2d_wgrad_ws_floats": (C.c_int, [_I] * 18 + [C.POINTER(C.c_int64)]),
     "bcos_conv2d_wgrad_ordered": (C.c_int, [_P, _P, _P, _P] + [_I] * 18 + [_P]),
+    "bcos_conv2d_wgrad_plan_query": (C.c_int, [_I] * 18 + [C.POINTER(WgradPlan)]),
     "bcos_colsum": (C.c_int, [_P, _P, _P, _P, _P, _L, _I, _P]),
     "bcos_colsum_ordered": (C.c_int, [_P, _P, _P, _P, _P, _L, _I, _P]),
     "bcos_colsum_ws_floats": (C.c_int, [_L, _I, C.POINTER(C.c_int64)]),
@@ -342,6 +350,15 @@ def route_query(ops, geom, epi):
     check(load().bcos_tapconv_route_query(C.byref(ops), C.byref(geom), C.byref(epi), C.byref(r)), "bcos_tapconv_route_query")
     return {"route": load().bcos_tapconv_route_name(r.route).decode(), "epi_kind": r.epi_kind, "norm": r.norm, "loop": LOOP_NAMES[r.loop],
             "bm": r.bm, "bn": r.bn, "chunks": r.chunks, "ch_pass": r.ch_pass}
+
+
+def wgrad_plan_query(N, H, W, C_, x_pitch, P, Q, Cout, g_pitch, kh, kw, sh, sw, ph, pw, dh, dw, gw_cin=0):
+    """What bcos_conv2d_wgrad_ordered would launch for this geometry: a dict of the fields of bcos_wgrad_plan
+    (bcos_conv2d_wgrad_plan_query; nothing is launched, no device is needed).  Raises BcosHipError where the launch would be rejected."""
+    r = WgradPlan()
+    check(load().bcos_conv2d_wgrad_plan_query(N, H, W, C_, x_pitch, P, Q, Cout, g_pitch, kh, kw, sh, sw, ph, pw, dh, dw, gw_cin, C.byref(r)),
+          "bcos_conv2d_wgrad_plan_query")
+    return {n: int(getattr(r, n)) for n, _ in WgradPlan._fields_ if n != "reserved"}
 
 
 def route_names():

@@ -243,6 +243,8 @@ struct WgradArgs {
                                    // (the 7 x 7 stem over 8 channels: 4 column tiles instead of 49 nearly empty ones)
     int cf;                        // ... channel stride of a tap among the fused columns: C rounded up to 4 (<= x_pitch; columns >= C are skipped)
     int ctot;                      // kh * kw * cf
+    int direct;                    // wgrad3_kernel: 1 = a 1 x 1 / stride-1 / unpadded layer over the whole image (P Q = H W): the input pixel IS the
+                                   // output pixel, no (n, i, j) counters (set by wgrad3_plan; wgrad_kernel does not read it)
 };
 
 constexpr int WG_T = 128;          // tile edge (channels)
@@ -463,7 +465,7 @@ __global__ __launch_bounds__(256, 3) void wgrad3_kernel(const WgradArgs p, float
     // (n, i, j) of the thread's four output pixels: divided out once, then ADVANCED by the 16 pixels of a stage (the two waves that stage
     // the input rows would otherwise spend eight integer divisions per thread and stage); a 1 x 1 / stride-1 / unpadded layer over the
     // whole image (P Q = H W) needs none of it: its input pixel IS the output pixel
-    const bool direct = p.kh * p.kw == 1 && p.sh == 1 && p.sw == 1 && p.ph == 0 && p.pw == 0 && p.P == p.H && p.Q == p.W;
+    const bool direct = p.direct != 0;
     int pn[4], pi[4], pj[4];
     if (is_x && !direct) {
 #pragma unroll
@@ -1143,6 +1145,7 @@ extern "C" int bcos_conv2d_wgrad(const float* glin, const float* x, float* gw, i
     const int tiles_co = (Cout + WG_T - 1) / WG_T;
     p.cf = (C + 3) & ~3;
     p.ctot = kh * kw * p.cf;
+    p.direct = 0;
     p.fuse = (p.cf < WG_T && kh * kw > 1 && x_pitch >= p.cf) ? 1 : 0;
     p.tiles_ci = ((p.fuse ? p.ctot : C) + WG_T - 1) / WG_T;
     const int grid_y = p.fuse ? 1 : kh * kw;
@@ -1170,7 +1173,12 @@ extern "C" int bcos_conv2d_wgrad(const float* glin, const float* x, float* gw, i
 
 // ---- round 6: the same weight gradient with the split at staging and a fixed-order combine (wgrad3_kernel) ------------------------------
 namespace {
-struct Wgrad3Plan { WgradArgs p; int tiles_co, grid_y; int64_t split, slab; };
+struct Wgrad3Plan {
+    WgradArgs p;
+    int tiles_co, grid_y;
+    int64_t split, slab;
+    int combine;                   // 0: one chunk, stored straight into gw; 1: wgrad_combine_kernel; 2: wgrad_combine_wide_kernel
+};
 
 int wgrad3_plan(Wgrad3Plan& pl, const float* glin, const float* x, float* gw, int N, int H, int W, int C, int x_pitch, int P, int Q, int Cout,
                 int g_pitch, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int gw_cin) {
@@ -1206,9 +1214,42 @@ int wgrad3_plan(Wgrad3Plan& pl, const float* glin, const float* x, float* gw, in
     p.chunk = (((p.M + split - 1) / split) + W3_K - 1) / W3_K * W3_K;
     pl.split = (p.M + p.chunk - 1) / p.chunk;
     pl.slab = (((int64_t)Cout * kh * kw * gw_cin) + 3) & ~(int64_t)3;
+    p.direct = (kh * kw == 1 && sh == 1 && sw == 1 && ph == 0 && pw == 0 && P == H && Q == W) ? 1 : 0;
+    // many slabs over a small gw: 16 threads per 16-byte column (wgrad_combine_wide_kernel); otherwise one thread per column
+    const int64_t n4 = (int64_t)Cout * kh * kw * gw_cin / 4;
+    pl.combine = pl.split == 1 ? 0 : (pl.split >= 32 && n4 <= ((int64_t)1 << 20)) ? 2 : 1;
+    return BCOS_OK;
+}
+
+// what bcos_conv2d_wgrad_ordered asks of gw beyond wgrad3_plan's geometry checks (the launch and the plan query share it)
+int wgrad3_dense_check(const Wgrad3Plan& pl) {
+    const WgradArgs& p = pl.p;
+    if ((int64_t)p.Cout * p.kh * p.kw * p.gw_cin % 4 != 0 || p.gw_cin != p.C)
+        return bcos_set_error(BCOS_E_NOSUP, "bcos_conv2d_wgrad_ordered: gw must be dense (gw_cin == C) and hold a multiple of 4 floats");
     return BCOS_OK;
 }
 }  // namespace
+
+extern "C" int bcos_conv2d_wgrad_plan_query(int N, int H, int W, int C, int x_pitch, int P, int Q, int Cout, int g_pitch, int kh, int kw,
+                                            int sh, int sw, int ph, int pw, int dh, int dw, int gw_cin, bcos_wgrad_plan* out) {
+    if (!out) return bcos_set_error(BCOS_E_INVAL, "bcos_conv2d_wgrad_plan_query: NULL result");
+    Wgrad3Plan pl;
+    int rc = wgrad3_plan(pl, nullptr, nullptr, nullptr, N, H, W, C, x_pitch, P, Q, Cout, g_pitch, kh, kw, sh, sw, ph, pw, dh, dw, gw_cin);
+    if (rc == BCOS_OK) rc = wgrad3_dense_check(pl);
+    if (rc != BCOS_OK) return rc;
+    out->fused_taps = pl.p.fuse;
+    out->direct = pl.p.direct;
+    out->tiles_co = pl.tiles_co;
+    out->tiles_ci = pl.p.tiles_ci;
+    out->grid_y = pl.grid_y;
+    out->split = (int32_t)pl.split;
+    out->combine = pl.combine;
+    out->reserved = 0;
+    out->chunk = pl.p.chunk;
+    out->last = pl.p.M - (pl.split - 1) * pl.p.chunk;
+    out->ws_floats = pl.split > 1 ? pl.split * pl.slab : 0;
+    return BCOS_OK;
+}
 
 extern "C" int bcos_conv2d_wgrad_ws_floats(int N, int H, int W, int C, int x_pitch, int P, int Q, int Cout, int g_pitch, int kh, int kw,
                                            int sh, int sw, int ph, int pw, int dh, int dw, int gw_cin, int64_t* floats) {
@@ -1232,8 +1273,8 @@ extern "C" int bcos_conv2d_wgrad_ordered(const float* glin, const float* x, floa
     const int rc = wgrad3_plan(pl, glin, x, gw, N, H, W, C, x_pitch, P, Q, Cout, g_pitch, kh, kw, sh, sw, ph, pw, dh, dw, gw_cin);
     if (rc != BCOS_OK) return rc;
     if (pl.split > 1 && !ws) return bcos_set_error(BCOS_E_INVAL, "bcos_conv2d_wgrad_ordered: this geometry needs a workspace (bcos_conv2d_wgrad_ws_floats)");
-    if ((int64_t)Cout * kh * kw * pl.p.gw_cin % 4 != 0 || pl.p.gw_cin != C)
-        return bcos_set_error(BCOS_E_NOSUP, "bcos_conv2d_wgrad_ordered: gw must be dense (gw_cin == C) and hold a multiple of 4 floats");
+    const int rcd = wgrad3_dense_check(pl);
+    if (rcd != BCOS_OK) return rcd;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const size_t lds = (size_t)2 * W3_BUF;
     static std::atomic<size_t> lds_hw;
@@ -1243,11 +1284,11 @@ extern "C" int bcos_conv2d_wgrad_ordered(const float* glin, const float* x, floa
     // one chunk: its slab IS gw (plain stores, every element written once: no zero fill either)
     hipLaunchKernelGGL(wgrad3_kernel, grid, dim3(256), lds, s, pl.p, pl.split > 1 ? ws : gw, pl.slab);
     int rc2 = check_launch("wgrad3 launch");
-    if (rc2 != BCOS_OK || pl.split == 1) return rc2;
+    if (rc2 != BCOS_OK || pl.combine == 0) return rc2;
     const int64_t n4 = (int64_t)Cout * kh * kw * pl.p.gw_cin / 4;
     int64_t blocks = (n4 + 255) / 256;
     if (blocks > 2048) blocks = 2048;
-    if (pl.split >= 32 && n4 <= ((int64_t)1 << 20))          // many slabs, small gw: 16 threads per column (wgrad_combine_wide_kernel)
+    if (pl.combine == 2)                                     // many slabs, small gw: 16 threads per column (wgrad_combine_wide_kernel)
         hipLaunchKernelGGL(wgrad_combine_wide_kernel, dim3((unsigned)((n4 + 15) / 16)), dim3(256), 0, s, reinterpret_cast<const f32x4*>(ws),
                            reinterpret_cast<f32x4*>(gw), n4, pl.slab / 4, (int)pl.split);
     else

@@ -754,7 +754,11 @@ int bcos_patch_norm_bwd(const float* x, const float* rnorm, float* out, int N, i
                         int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, void* stream);
 /* The same plus a gradient that reaches the same tensor by another path: out = x * PatchSum^T(rnorm) + addend (addend [N,H,W,C] dense,
  * may be NULL) -- the shortcut gradient of a residual block folded into the patch-norm term of the block's first convolution, one
- * elementwise pass less per block and training step.  (ABI v8) */
+ * elementwise pass less per block and training step.  (ABI v8)
+ * Accuracy, every element, with u = 2^-24, T the patch sum and S the same sum over |rnorm|:
+ *     |out - exact| <= (kh kw + 2) u (|x| S + |addend|)
+ * (at most kh kw - 1 additions in any order, one product, one sum); a pixel that no patch contains gives exactly the addend, or 0.
+ * Pad channels C .. x_pitch-1 of x are not read.  tests/test_wgrad_gpu.py: every kernel variant on rectangular geometry. */
 int bcos_patch_norm_bwd_add(const float* x, const float* rnorm, const float* addend, float* out, int N, int H, int W, int C, int x_pitch,
                             int P, int Q, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, void* stream);
 
@@ -762,7 +766,24 @@ int bcos_patch_norm_bwd_add(const float* x, const float* rnorm, const float* add
  * glin[n,i,j,co] * x[n, i*sh - ph + th*dh, j*sw - pw + tw*dw, ci]   (the autograd convolution_backward weight branch).
  * glin [N,P,Q,g_pitch] (Cout used), x [N,H,W,x_pitch] (C used), gw [Cout][kh][kw][gw_cin] fp32, ZEROED BY THE CALLER
  * (partial sums of pixel chunks are combined with atomics).  Pitches 0 = dense.  Exact fp32 products on
- * v_mfma_f32_32x32x2_f32; a linear layer is the 1x1 case with N = 1, H = 1, W = rows. */
+ * v_mfma_f32_32x32x2_f32 in contraction mode f32, the six leading products of exact 3-way bf16 splits otherwise; a linear layer is the
+ * 1x1 case with N = 1, H = 1, W = rows.  gw_cin >= C (0 = C): columns C .. gw_cin-1 of gw are not touched.
+ * Only channels 0 .. C-1 of x and 0 .. Cout-1 of glin enter the result: the pad channels up to the pitches may hold anything, NaN
+ * included (the fused-tap route loads x up to C rounded up to 4, into tile columns whose sums are never stored).
+ * Accuracy, every element, for this entry point in either mode and for bcos_conv2d_wgrad_ordered: with u = 2^-24 and
+ *     form[co,th,tw,ci] = sum over output pixels (n,i,j) of |glin[n,i,j,co]| * |x[n, i*sh-ph+th*dh, j*sw-pw+tw*dw, ci]|
+ * (the L1 form of the column sums below),
+ *     |gw - exact| <= K u form,
+ * K = max(4 x the worst use of the form by PyTorch's own fp32 weight gradient, 16) per family of inputs of tests/wgrad_cases.py:
+ * 20.8 for normal data, 26.4 with images 2^24 apart in magnitude, 259.6 with single pixels 2^12 above the rest (fp32 itself loses the
+ * ordinary pixels behind them), and the floor 16 -- twice the 2^-21 |a b| = 8 u that the three dropped products of a split cost -- for
+ * operands of ONE sign.  For those, and only on the bf16 matrix pipe (modes bf16x3 / f16x2), the bound grows with the accumulations
+ * D behind an element: |gw - exact| <= (16 + D) u form, D = 6 ceil(chunk / 16) + chunks - 1 (six matrix instructions per 16 pixels of
+ * a pixel chunk, then the sum over the chunks): the pipe's fp32 accumulation costs 0.2 - 0.5 u of the running sum per instruction
+ * (measured: the error of one-signed data is linear in D and depends on nothing else), which cancels on data of mixed sign and does
+ * not where every term has the same sign.  Mode f32 needs no such term (1.0 u measured on the same data).
+ * An element whose sum is empty (a tap that only ever meets padding) is exactly 0.
+ * tests/test_wgrad_gpu.py holds every route of both entry points to this, element by element. */
 int bcos_conv2d_wgrad(const float* glin, const float* x, float* gw, int N, int H, int W, int C, int x_pitch, int P, int Q,
                       int Cout, int g_pitch, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int gw_cin,
                       void* stream);
@@ -778,6 +799,26 @@ int bcos_conv2d_wgrad_ws_floats(int N, int H, int W, int C, int x_pitch, int P, 
 int bcos_conv2d_wgrad_ordered(const float* glin, const float* x, float* gw, float* ws, int N, int H, int W, int C, int x_pitch, int P,
                               int Q, int Cout, int g_pitch, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int gw_cin,
                               void* stream);
+
+/* What bcos_conv2d_wgrad_ordered would launch for a geometry (additive, ABI v12; host only: nothing is launched, no device is needed).
+ * The launch reads the same plan, so the two cannot disagree.  out == NULL: BCOS_E_INVAL; otherwise the codes of the launch's geometry
+ * validation (BCOS_E_INVAL for sizes and pitches, BCOS_E_NOSUP for a gw that is not dense or no multiple of 4 floats).  The plan depends
+ * on BCOS_OPT_WGRAD_WGS. */
+typedef struct bcos_wgrad_plan {
+    int32_t fused_taps;   /* 1: C < 128 with several taps -- the tile's columns run over (tap, channel) pairs; 0: one tap per workgroup   */
+    int32_t direct;       /* 1: 1x1 / stride 1 / unpadded over the whole image: input pixel = output pixel; 0: (n, i, j) counters        */
+    int32_t tiles_co;     /* 128-row tiles over Cout                                                                                     */
+    int32_t tiles_ci;     /* 128-column tiles over C, or over kh kw (C rounded up to 4) when fused_taps                                  */
+    int32_t grid_y;       /* taps per launch dimension: kh kw, or 1 when fused_taps                                                      */
+    int32_t split;        /* pixel chunks (= slabs of the workspace when > 1)                                                            */
+    int32_t combine;      /* 0: one chunk stored into gw; 1: wgrad_combine_kernel; 2: wgrad_combine_wide_kernel                          */
+    int32_t reserved;     /* 0                                                                                                           */
+    int64_t chunk;        /* output pixels per chunk (a multiple of 16)                                                                  */
+    int64_t last;         /* output pixels of the last chunk (1 .. chunk)                                                                */
+    int64_t ws_floats;    /* what bcos_conv2d_wgrad_ws_floats returns                                                                    */
+} bcos_wgrad_plan;
+int bcos_conv2d_wgrad_plan_query(int N, int H, int W, int C, int x_pitch, int P, int Q, int Cout, int g_pitch, int kh, int kw, int sh,
+                                 int sw, int ph, int pw, int dh, int dw, int gw_cin, bcos_wgrad_plan* out);
 
 /* out[c] += sum_r (a[r,c] - shift_a[c]) * (b ? b[r,c] - shift_b[c] : 1), C % 4 == 0, `out` zeroed by the caller: bias
  * gradients (sum of glin) and the batch statistics / parameter gradients of BatchNormUncentered2d in training mode
