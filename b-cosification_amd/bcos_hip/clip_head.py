@@ -104,3 +104,27 @@ def zeroshot_attribution(engine, images: torch.Tensor, text_weights: torch.Tenso
     out = engine.explain(images, want_weights=want_weights, gates=gates, cotangent=head)
     return dict(logits=info["logits"], explained_class_idx=info["cls"], embedding=out["embedding"],
                 dynamic_linear_weights=out["dynamic_linear_weights"], contribution_map=out["contribution_map"])
+
+
+def distill_loss(student_out: torch.Tensor, teacher_out: torch.Tensor, *, logit_scale_value: float = 10.0, logit_bias_value: float = -10.0,
+                 cos_power: int = 0, logit_scale=None, logit_bias=None) -> torch.Tensor:
+    """The distillation objective of the CLIP B-cosification recipe's training step (bcos/training/trainer.py:673-707) as one call:
+    both outputs L2-normalised and SigLipLoss between them, loss and every gradient from ONE bcos_siglip_loss call (BCOS_SIGLIP_NORMALIZE:
+    the normalised features are never stored).
+
+    `student_out`: the B-cos tower's output -- [N, D] (attnpool head) or [(HW), N, D] (attn_unpool head: every location's cosine to the
+    power `cos_power`, averaged; 0 stands for the recipe's default 1; the pooled head ignores it, as the step does).  `teacher_out` [N, D]:
+    the frozen CLIP tower's embedding.  Fixed scale and bias (fixed_logit_scale / fixed_logit_bias, the recipe's default) are
+    `logit_scale_value` / `logit_bias_value`; the learnable variant passes the model's parameters: `logit_scale` the LOGARITHM of the
+    scale (model.logit_scale: its exp() is taken here, under autograd) and `logit_bias`, one-element float32 device tensors that receive
+    their gradients.  This goes behind `train_plan.train_forward(eng, x)`."""
+    if cos_power != int(cos_power) or cos_power < 0:
+        raise ValueError(f"distill_loss: cos_power must be a non-negative integer, got {cos_power} (a fractional power of a negative "
+                         "cosine is NaN in the reference)")
+    ops.require_device(student_out, "distill_loss")
+    if student_out.dim() not in (2, 3) or teacher_out.dim() != 2:
+        raise ValueError(f"distill_loss: student [N, D] or [(HW), N, D], teacher [N, D]; got {tuple(student_out.shape)}, {tuple(teacher_out.shape)}")
+    p = max(int(cos_power), 1) if student_out.dim() == 3 else 0
+    scale = logit_scale_value if logit_scale is None else logit_scale.exp()
+    bias = logit_bias_value if logit_bias is None else logit_bias
+    return ops.siglip_loss(student_out, teacher_out, scale, bias, pos_offset=0, p=p, normalize=True)

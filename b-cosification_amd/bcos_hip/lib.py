@@ -19,7 +19,8 @@ LIB_PATH = Path(os.environ["BCOS_HIP_LIB"]) if os.environ.get("BCOS_HIP_LIB") el
 CSRC = PKG_ROOT / "csrc"
 INCLUDE = REPO_ROOT / "include"
 SOURCES = ["bcos_tapconv.hip", "bcos_skinny.hip", "bcos_elementwise.hip", "bcos_vit.hip", "bcos_render.hip", "bcos_train.hip",
-           "bcos_agc.hip", "bcos_occlusion.hip", "bcos_rise.hip", "bcos_perturb.hip", "bcos_head.hip", "bcos_boundary.hip", "bcos_shortcut.hip", "bcos_dense.hip", "bcos_abi.hip"]
+           "bcos_agc.hip", "bcos_occlusion.hip", "bcos_rise.hip", "bcos_perturb.hip", "bcos_head.hip", "bcos_boundary.hip", "bcos_shortcut.hip", "bcos_dense.hip", "bcos_siglip.hip",
+           "bcos_abi.hip"]
 
 BCOS_NONE, BCOS_CONV_EPS, BCOS_LINEAR_EPS = 0, 1, 2
 BCOS_EPI_NORM_ONLY = 1
@@ -28,6 +29,7 @@ BCOS_EPI_SCALE_GATE_LSB = 4
 BCOS_EPI_GATE2_FROM_MUL = 8
 BCOS_EPI_MUL_FROM_ACT = 16
 BCOS_EPI_UNIT_NORM_W = 32
+BCOS_SIGLIP_NORMALIZE, BCOS_SIGLIP_DETACH_POW = 1, 2
 BCOS_E_INVAL = -22
 BCOS_E_NOSUP = -95
 ABI_VERSION = 12
@@ -219,6 +221,8 @@ SIGNATURES = {
     "bcos_bn_reader_finish": (C.c_int, [_P, _P, _P, _P, _P, _I, _F, _F, _P]),
     "bcos_slice_relu_bwd_colsums": (C.c_int, [_P, _P, _L, _P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _I, _P]),
     "bcos_slice_bn_bwd_acc": (C.c_int, [_P, _P, _L, _P, _P, _P, _P, _P, _L, _L, _I, _I, _P]),
+    "bcos_siglip_loss": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "bcos_siglip_loss_ws_floats": (C.c_int, [_I, _I, _I, _I, C.POINTER(C.c_int64)]),
 }
 
 _lib = None

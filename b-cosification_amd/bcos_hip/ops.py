@@ -2345,3 +2345,87 @@ def localisation_fractions(attr: torch.Tensor, cell_h: int, cell_w: int, neg: bo
                                              int(cell_h), int(cell_w), 1 if neg else 0, _stream()),
              "bcos_localisation_fractions")
     return out
+
+
+# ---------------------------------------------------------------------------------------------- SigLIP distillation loss
+_SIGLIP_WS = {}                    # (device, stream) -> workspace of siglip_loss (launches of one stream run in order: one buffer)
+_SIGLIP_CONST = {}                 # (device, value) -> the 0-d device tensor of a scale / bias given as a Python number
+
+
+def _siglip_workspace(floats: int, device, stream) -> torch.Tensor:
+    key = (device.index, stream.value)
+    buf = _SIGLIP_WS.get(key)
+    if buf is None or buf.numel() < floats:
+        buf = torch.empty(max(int(floats), 1 << 19), device=device, dtype=torch.float32)
+        _SIGLIP_WS[key] = buf
+    return buf
+
+
+def _siglip_scalar(v, device, what):
+    if torch.is_tensor(v):
+        if v.numel() != 1:
+            raise BcosHipError(f"siglip_loss: {what} is a number or a tensor of one element, got shape {tuple(v.shape)}")
+        if v.device != device or v.dtype != torch.float32:
+            raise BcosHipError(f"siglip_loss: {what} must be a float32 tensor on {device}, got {v.dtype} on {v.device}")
+        return v
+    key = (device.index, float(v))
+    t = _SIGLIP_CONST.get(key)
+    if t is None:
+        t = _SIGLIP_CONST[key] = torch.full((), float(v), device=device, dtype=torch.float32)
+    return t
+
+
+class _SiglipLoss(torch.autograd.Function):
+    """loss and the wanted gradients come out of the one call of the forward; the backward only scales them by grad_output"""
+
+    @staticmethod
+    def forward(ctx, s, t, scale, bias, pos_offset, p, flags):
+        lib = _l.load()
+        L, N, D = s.shape
+        M = t.shape[0]
+        need = C.c_int64(0)
+        _l.check(lib.bcos_siglip_loss_ws_floats(L, N, M, D, C.byref(need)), "bcos_siglip_loss_ws_floats")
+        st = _stream()
+        ws = _siglip_workspace(need.value, s.device, st)
+        want = ctx.needs_input_grad[:4]
+        loss = torch.empty((), device=s.device, dtype=torch.float32)
+        gs = torch.empty_like(s) if want[0] else None
+        gt = torch.empty_like(t) if want[1] else None
+        gsc = torch.empty((), device=s.device, dtype=torch.float32) if want[2] else None
+        gb = torch.empty((), device=s.device, dtype=torch.float32) if want[3] else None
+        _l.check(lib.bcos_siglip_loss(_dev(s, "siglip_loss.s"), _dev(t, "siglip_loss.t"), _dev(scale, "siglip_loss.scale", False),
+                                      _dev(bias, "siglip_loss.bias", False), _dev(loss, "loss"), _dev(gs, "gs"), _dev(gt, "gt"),
+                                      _dev(gsc, "gscale"), _dev(gb, "gbias"), _dev(ws, "ws"), ws.numel(), L, N, M, D, int(pos_offset),
+                                      int(p), int(flags), st), "bcos_siglip_loss")
+        ctx.grads = (gs, gt, gsc, gb)
+        ctx.shapes = (scale.shape, bias.shape)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gout):
+        gs, gt, gsc, gb = ctx.grads
+        return (None if gs is None else gs * gout, None if gt is None else gt * gout,
+                None if gsc is None else (gsc * gout).reshape(ctx.shapes[0]), None if gb is None else (gb * gout).reshape(ctx.shapes[1]),
+                None, None, None)
+
+
+def siglip_loss(s, t, scale, bias, *, pos_offset=0, p=0, normalize=False, detach_pow=False):
+    """The SigLIP pair loss between student features s ([N, D], or [L, N, D]: one vector per location of the attn_unpool head) and
+    teacher / text features t [M, D], with its gradients, as one call of bcos_siglip_loss (include/bcos_hip.h):
+        z_ij = scale * q_ij + bias,  q = the cosine (p = 0) or mean_l c |c|^(p-1) (p >= 1);  loss = -sum logsigmoid(y_ij z_ij) / N,
+        y = +1 in column pos_offset + i of row i, -1 elsewhere (pos_offset < 0: no positives).
+    `scale` / `bias`: Python numbers or one-element float32 device tensors; they receive gradients when they require them, as s and t do.
+    `normalize`: both operands are L2-normalised inside the call (F.normalize, eps 1e-12), gradients through it.  `detach_pow`: the factor
+    |c|^(p-1) is a constant in the gradient.  A 0-d float32 device tensor; differentiable once (the gradients are computed with the loss)."""
+    if not (torch.is_tensor(s) and torch.is_tensor(t)):
+        raise BcosHipError("siglip_loss: s and t are tensors")
+    require_device(s, "siglip_loss")
+    require_device(t, "siglip_loss")
+    if s.dim() not in (2, 3) or t.dim() != 2 or s.shape[-1] != t.shape[-1] or t.device != s.device:
+        raise BcosHipError(f"siglip_loss: s is [N, D] or [L, N, D] and t [M, D] on one device, got {tuple(s.shape)} and {tuple(t.shape)}")
+    if int(p) != p or p < 0:
+        raise BcosHipError(f"siglip_loss: p is a non-negative integer (a fractional power of a negative cosine is NaN), got {p}")
+    s3 = s.contiguous().view((1,) + tuple(s.shape)) if s.dim() == 2 else s.contiguous()
+    flags = (_l.BCOS_SIGLIP_NORMALIZE if normalize else 0) | (_l.BCOS_SIGLIP_DETACH_POW if detach_pow else 0)
+    sc, bi = _siglip_scalar(scale, s.device, "scale"), _siglip_scalar(bias, s.device, "bias")
+    return _SiglipLoss.apply(s3, t.contiguous(), sc, bi, int(pos_offset), int(p), flags)

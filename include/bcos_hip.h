@@ -1234,6 +1234,37 @@ int bcos_prep_input_perturbed(const float* x, const float* scores, const uint64_
  * BCOS_E_INVAL: a NULL pointer, R / CL / group <= 0, R not a multiple of group, mode outside 0..2. */
 int bcos_class_scores(const float* logits, const int32_t* targets, int group, int mode, float* out, int64_t R, int CL, void* stream);
 
+/* -- training recipe: the SigLIP distillation objective of the CLIP recipe (additive entry points of ABI v12) ------------------------- */
+/* SigLipLoss (bcos/modules/losses.py:576-638: get_ground_truth :606-610, get_logits :612-624, _loss :626-638, the multi-rank sum of
+ * forward :640-694) together with the two F.normalize of the training step that calls it (bcos/training/trainer.py:673-674, 699-707),
+ * loss and every gradient in one call.
+ *   s [L, N, D]  student features: L = 1 the pooled head, L = HW the attn_unpool layout [(HW), N, D];   t [M, D]  teacher features;
+ *   scale, bias  one DEVICE float each (the recipe's learnable variant makes them parameters: model.logit_scale.exp(), model.logit_bias);
+ *   pos_offset   column pos_offset + i is row i's positive (label y = +1), every other column y = -1; pos_offset < 0: no positives (the
+ *                reference's negative_only).  M = W N with pos_offset = rank N is the whole multi-rank loss: the local term plus the
+ *                negative_only terms against the other ranks' features, every term divided by N;
+ *   p            0: z_ij = scale c_ij + bias (L must be 1);  p >= 1: z_ij = scale mean_l(c_lij |c_lij|^(p-1)) + bias (cos_scaling = p);
+ *   flags        BCOS_SIGLIP_NORMALIZE: c is taken between u = x / max(||x||_2, 1e-12) of both operands (IEEE divisions, as F.normalize: a
+ *                one-element row is exactly +-1) and the gradients go through the normalisation (a row below the clamp gets g / 1e-12, its norm held constant, as torch's autograd returns);
+ *                BCOS_SIGLIP_DETACH_POW: the factor |c|^(p-1) is a constant in the gradient (the reference's self.detach).
+ *   loss = -sum_ij logsigmoid(y_ij z_ij) / N, logsigmoid(x) = min(x, 0) - log1p(exp(-|x|));   G_ij = -y_ij sigmoid(-y_ij z_ij) / N;
+ *   gbias = sum G;  gscale = sum G_ij q_ij with q the pooled cosine (z - bias) / scale, taken before the scaling, not by that division;
+ *   gs [L, N, D], gt [M, D]: through the mean, the power and the normalisation.  gs, gt, gscale, gbias: NULL = not wanted.
+ * Order of every sum, a function of (L, N, M, D) alone: a dot product over D as 64 lane chains d = lane, lane + 64, ... (FMA) combined
+ * by the butterfly xor 32, 16, 8, 4, 2, 1; a row's sums over M likewise over j; the mean over l ascending; gs over j ascending; gt over
+ * (l, i) with l outer; the three scalars over the rows' partial sums as lane chains and the butterfly.  No atomics: two calls on the
+ * same data give the same bits.  Three launches; ws (bcos_siglip_loss_ws_floats floats, owned by the caller) is written before it is
+ * read, nothing is allocated, copied or synchronised.
+ * BCOS_E_INVAL (before anything is launched): NULL s / t / loss / scale / bias, a size <= 0 or L N M, L N D or M D above 2^38,
+ * pos_offset + N > M, p outside [0, 64], L > 1 with p = 0, an unknown flag, ws NULL or ws_floats too small. */
+#define BCOS_SIGLIP_NORMALIZE 1
+#define BCOS_SIGLIP_DETACH_POW 2
+int bcos_siglip_loss(const float* s, const float* t, const float* scale, const float* bias, float* loss, float* gs, float* gt,
+                     float* gscale, float* gbias, float* ws, int64_t ws_floats, int L, int N, int M, int D, int pos_offset, int p,
+                     int flags, void* stream);
+/* floats = (L N + M) (D + 1) + 2 L N M + N M + 3 N.  BCOS_E_INVAL: floats NULL or sizes that bcos_siglip_loss refuses. */
+int bcos_siglip_loss_ws_floats(int L, int N, int M, int D, int64_t* floats);
+
 #ifdef __cplusplus
 }
 #endif
