@@ -21,6 +21,8 @@ INCLUDE = REPO_ROOT / "include"
 SOURCES = ["bcos_tapconv.hip", "bcos_skinny.hip", "bcos_elementwise.hip", "bcos_vit.hip", "bcos_render.hip", "bcos_train.hip",
            "bcos_agc.hip", "bcos_occlusion.hip", "bcos_rise.hip", "bcos_perturb.hip", "bcos_head.hip", "bcos_boundary.hip", "bcos_shortcut.hip", "bcos_dense.hip", "bcos_siglip.hip",
            "bcos_abi.hip"]
+# every header a source may include -- all of csrc/*.h and the ABI header: an edit of any of them rebuilds every object
+HEADERS = sorted(CSRC.glob("*.h")) + [INCLUDE / "bcos_hip.h"]
 
 BCOS_NONE, BCOS_CONV_EPS, BCOS_LINEAR_EPS = 0, 1, 2
 BCOS_EPI_NORM_ONLY = 1
@@ -231,7 +233,7 @@ _lib = None
 def build(force: bool = False, verbose: bool = False) -> Path:
     """Compile csrc/*.hip for gfx950 into lib/libbcos_hip.so (hipcc cross-compiles without a GPU)."""
     srcs = [CSRC / s for s in SOURCES]
-    deps = srcs + [CSRC / "bcos_rise_mask.h", CSRC / "bcos_internal.h", INCLUDE / "bcos_hip.h"]
+    deps = srcs + HEADERS
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     # the compiler flags are part of the build's identity: objects (and the library) built with other BCOS_HIPCC_FLAGS are
     # never reused -- the flags are recorded in a stamp file next to the objects and a change forces a full rebuild
@@ -258,7 +260,7 @@ def build(force: bool = False, verbose: bool = False) -> Path:
         for k in parts:
             obj = objdir / (s.stem + ("" if k is None else f"_p{k}") + ".o")
             extra = [] if k is None else [f"-DBCOS_TAPCONV_PART={k}"]
-            stale = force or not obj.exists() or any(obj.stat().st_mtime < d.stat().st_mtime for d in (s, deps[-3], deps[-2], deps[-1]))
+            stale = force or not obj.exists() or any(obj.stat().st_mtime < d.stat().st_mtime for d in [s] + HEADERS)
             jobs.append((obj, [hipcc] + flags + extra + ["-c", str(s), "-o", str(obj)], stale))
     from concurrent.futures import ThreadPoolExecutor
 

@@ -10,8 +10,7 @@
 #include <stdint.h>
 #include "bcos_hip.h"
 #include "bcos_internal.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "bcos_f16x2.h"
 
 namespace {
 

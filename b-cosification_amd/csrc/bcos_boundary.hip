@@ -7,8 +7,9 @@
 // The result is bit for bit what the two bcos_tapconv_ops launches give (tests/test_boundary_fusion_gpu.py): per accumulator the same 16-k
 // steps in the same order with the same three products per step (l_a h_b, h_a l_b, h_a h_b), the same operand-scale rule (a power of two
 // from the row's max |A|: per-pixel maxima of g1, the row maximum of G), the same split into (h, l) f16 and the same epilogue expressions
-// in the same order as the specialised epilogues of bcos_tapconv.hip (kinds MUL | ADDEND | OUT2 [| MUL2] and MUL [| MULACT]).  split4_f16, the scale
-// rule and the rebuilt multiplier are restated here; they must stay what bcos_tapconv.hip has.
+// in the same order as the specialised epilogues of bcos_tapconv.hip (kinds MUL | ADDEND | OUT2 [| MUL2] and MUL [| MULACT]).  The split, the
+// scale rule, the lane-group maximum and the rebuilt multiplier are the definitions both files share (bcos_f16x2.h); what is restated here
+// is the order of the epilogue expressions and nothing else.
 //
 // Shape: 256 threads = 2 x 2 waves, one 64-row tile per workgroup, 67 KB of LDS (two workgroups per CU).
 //   phase 1  [64 x 64] x [64 x 256]: a wave owns 32 rows x 128 columns (4 accumulator tiles).  A fragments (K = 64: 8 x 16 bytes per lane) and
@@ -37,11 +38,7 @@
 #include <atomic>
 #include "bcos_hip.h"
 #include "bcos_internal.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+#include "bcos_f16x2.h"
 
 namespace {
 
@@ -61,51 +58,6 @@ struct BArgs {
     float* g3; unsigned* g3_absmax; unsigned* g3_imgmax; unsigned* g3_imgmin_c;
     int M, PQ;
 };
-
-// max over the 32 lanes of each half of a wave on the vector ALU (DPP); lanes 16 and 48 hold the result (bcos_tapconv.hip: group_max_u32<32>)
-__device__ __forceinline__ unsigned half_max_u32(unsigned v) {
-    v = max(v, (unsigned)__builtin_amdgcn_update_dpp((int)v, (int)v, 0xB1, 0xF, 0xF, false));       // quad_perm [1,0,3,2]
-    v = max(v, (unsigned)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x4E, 0xF, 0xF, false));       // quad_perm [2,3,0,1]
-    v = max(v, (unsigned)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x141, 0xF, 0xF, false));      // row_half_mirror
-    v = max(v, (unsigned)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x140, 0xF, 0xF, false));      // row_mirror
-    v = max(v, (unsigned)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x142, 0xA, 0xF, false));      // row_bcast15 into rows 1 and 3
-    return v;
-}
-
-// four fp32 values -> (h, l) f16 pairs with h = f16(x s), l = f16(x s - h): the instructions of bcos_tapconv.hip's split4_f16<false>
-__device__ __forceinline__ void split4_f16(const f32x4& x, const float s, unsigned& h01, unsigned& h23, unsigned& l01, unsigned& l23) {
-    unsigned a, b, c, d;
-    asm("v_fma_mixlo_f16 %0, %4, %8, 0\n\t"
-        "v_fma_mixlo_f16 %1, %6, %8, 0\n\t"
-        "v_fma_mixhi_f16 %0, %5, %8, 0\n\t"
-        "v_fma_mixhi_f16 %1, %7, %8, 0\n\t"
-        "v_fma_mixlo_f16 %2, %4, %8, -%0 op_sel_hi:[0,0,1]\n\t"
-        "v_fma_mixlo_f16 %3, %6, %8, -%1 op_sel_hi:[0,0,1]\n\t"
-        "v_fma_mixhi_f16 %2, %5, %8, -%0 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\t"
-        "v_fma_mixhi_f16 %3, %7, %8, -%1 op_sel:[0,0,1] op_sel_hi:[0,0,1]"
-        : "=&v"(a), "=&v"(b), "=&v"(c), "=&v"(d)
-        : "v"(x[0]), "v"(x[1]), "v"(x[2]), "v"(x[3]), "v"(s));
-    h01 = a; h23 = b; l01 = c; l23 = d;
-}
-
-// the eight k of a lane's fragment (two 16-byte pieces) -> its h and l fragments
-__device__ __forceinline__ void split_frag(const f32x4& x0, const f32x4& x1, const float s, f16x8& h, f16x8& l) {
-    unsigned h01, h23, h45, h67, l01, l23, l45, l67;
-    split4_f16(x0, s, h01, h23, l01, l23);
-    split4_f16(x1, s, h45, h67, l45, l67);
-    h = __builtin_bit_cast(f16x8, u32x4{h01, h23, h45, h67});
-    l = __builtin_bit_cast(f16x8, u32x4{l01, l23, l45, l67});
-}
-
-// operand scale of a row from the bit pattern of its max |A|: max * scale in [2^14, 2^15); and the inverse of such a scale
-__device__ __forceinline__ float row_scale_of(unsigned maxbits) {
-    unsigned E = maxbits >> 23;
-    E = E < 15u ? 15u : E;
-    return __uint_as_float((268u - E) << 23);
-}
-__device__ __forceinline__ float inv_scale(float s) { return __uint_as_float((254u - (__float_as_uint(s) >> 23)) << 23); }
-
-__device__ __forceinline__ unsigned absbits(float v) { return __float_as_uint(v) & 0x7fffffffu; }
 
 __global__ __launch_bounds__(NT, 2) void boundary_conv3_kernel(const BArgs p) {
 #pragma clang fp contract(off)
@@ -213,8 +165,8 @@ __global__ __launch_bounds__(NT, 2) void boundary_conv3_kernel(const BArgs p) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const int lrow = wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * fhalf;
-        const unsigned a = half_max_u32(mxg[r]);
-        const unsigned b = want2 ? half_max_u32(mx2[r]) : 0u;
+        const unsigned a = group_max_u32<32>(mxg[r]);
+        const unsigned b = want2 ? group_max_u32<32>(mx2[r]) : 0u;
         if (frow == 16) { sMaxG[wn * BM + lrow] = a; sMax2[wn * BM + lrow] = b; }
     }
     __syncthreads();                   // G and the row maxima of both column waves are complete
@@ -264,18 +216,14 @@ __global__ __launch_bounds__(NT, 2) void boundary_conv3_kernel(const BArgs p) {
             const int lrow = wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * fhalf;
             const float ai = inv_scale(row_scale_of(max(sMaxG[lrow], sMaxG[BM + lrow])));
             float m1 = tt[r];
-            if (rebuild) {             // t = csc sqrt(|a - csh| / (|csc| norm)) where the kept activation a is positive (BCOS_EPI_MUL_FROM_ACT)
-                const float a = tt[r];
-                const float den = fabsf(mcsc) * mn[r];
-                m1 = (a > 0.f && den > 0.f) ? mcsc * __builtin_amdgcn_sqrtf(fabsf(a - mcsh) * __builtin_amdgcn_rcpf(den)) : 0.f;
-            }
+            if (rebuild) m1 = bcos_mul_from_act(tt[r], mn[r], mcsc, mcsh);      // t2 holds the kept activation (BCOS_EPI_MUL_FROM_ACT)
             float v = acc3[r] * ai;
             v = v * cinv;
             const float val = v + 0.f;
             const float o = val * m1;
             __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(o), r_g3, voff[r], 0, 0);
             if (want3) {
-                const unsigned a1 = half_max_u32(absbits(o));
+                const unsigned a1 = group_max_u32<32>(absbits(o));
                 if (frow == 16) sMax3[wn * BM + lrow] = a1;
             }
         }

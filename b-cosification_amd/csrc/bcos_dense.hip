@@ -10,22 +10,15 @@
 #include <type_traits>
 #include "bcos_hip.h"
 #include "bcos_internal.h"
+#include "bcos_f16x2.h"
 
 // x * scale + shift is TWO roundings here, as in bcos_channel_affine_rows (bcos_train.hip), whose bits bcos_slice_affine_rows must
 // reproduce; and the gate of the backward kernel is decided on exactly the value the forward kernel compared with zero.
 #pragma clang fp contract(off)
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 namespace {
 
 constexpr int MAX_LDS_C = 8192;            // scale + shift of the looping form: 2 x 32 KiB of dynamic LDS at most
-
-inline int check_launch(const char* what) {
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return bcos_set_hip_error(what, err);
-    return BCOS_OK;
-}
 
 // per-channel constants of one lane: registers when the lane's channel quad is the same for every row (LPR < 64), LDS otherwise
 template <int LPR>

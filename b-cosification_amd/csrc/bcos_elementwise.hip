@@ -6,8 +6,7 @@
 #include <stdint.h>
 #include "bcos_hip.h"
 #include "bcos_internal.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "bcos_f16x2.h"
 
 namespace {
 
@@ -30,12 +29,6 @@ inline unsigned grid_for(int64_t work_items) {
     return (unsigned)b;
 }
 
-inline int check_launch(const char* what) {
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return bcos_set_hip_error(what, err);
-    return BCOS_OK;
-}
-
 // ---- unit-norm weight projection: one wavefront per row --------------------------------
 __global__ __launch_bounds__(TPB) void weight_rownorm_kernel(const float* __restrict__ w,
                                                              const float* __restrict__ gain,
@@ -47,8 +40,7 @@ __global__ __launch_bounds__(TPB) void weight_rownorm_kernel(const float* __rest
         const float* src = w + (int64_t)r * cols;
         float ss = 0.f;
         for (int64_t c = lane; c < cols; c += 64) ss = fmaf(src[c], src[c], ss);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o);
+        ss = wave_sum(ss);
         const float nrm = sqrtf(ss);
         const float gn = gain ? gain[r] : 1.f;
         float* dst = out + (int64_t)r * cols;
@@ -263,8 +255,7 @@ __global__ __launch_bounds__(TPB) void avgpool_fwd_row_kernel(const float* __res
         acc = acc / pool;
         if (live) y4[i] = acc;
         if (absmax) {
-            unsigned m = max(max(__float_as_uint(acc[0]) & 0x7fffffffu, __float_as_uint(acc[1]) & 0x7fffffffu),
-                             max(__float_as_uint(acc[2]) & 0x7fffffffu, __float_as_uint(acc[3]) & 0x7fffffffu));
+            unsigned m = absbits4(acc);
             for (int o = C4 >> 1; o >= 1; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o));
             if (live && c4 == 0) absmax[(int64_t)blockIdx.x * OW + ow] = m;
         }
@@ -385,8 +376,7 @@ __global__ __launch_bounds__(TPB) void avgpool_bwd_win_kernel(const float* __res
             const int i = i0 + u * TPB + threadIdx.x;
             if (live[u]) gx4[i] = acc;
             if (absmax) {
-                unsigned m = max(max(__float_as_uint(acc[0]) & 0x7fffffffu, __float_as_uint(acc[1]) & 0x7fffffffu),
-                                 max(__float_as_uint(acc[2]) & 0x7fffffffu, __float_as_uint(acc[3]) & 0x7fffffffu));
+                unsigned m = absbits4(acc);
                 for (int o = C4 >> 1; o >= 1; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o));
                 if (live[u] && cq[u] == 0) absmax[((int64_t)n * H + h) * W + wq[u]] = m;
             }
@@ -656,8 +646,7 @@ __global__ __launch_bounds__(TPB) void weight_row_invnorm_kernel(const float* __
         const float* src = w + (int64_t)r * cols;
         float ss = 0.f;
         for (int64_t c = lane; c < cols; c += 64) ss = fmaf(src[c], src[c], ss);       // (the summation order of weight_rownorm_kernel)
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o);
+        ss = wave_sum(ss);
         if (lane == 0) inv[r] = (gain ? gain[r] : 1.f) / sqrtf(ss);
     }
 }

@@ -10,19 +10,12 @@
 #include <stdint.h>
 #include "bcos_hip.h"
 #include "bcos_internal.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "bcos_f16x2.h"
 
 namespace {
 
 constexpr int MAX_TERMS = 8;                 // include/bcos_hip.h: 1 <= J <= 8
 constexpr int64_t MAX_HEAD_BLOCKS = 16384;   // (the grid of head_rank1_kernel, bcos_elementwise.hip)
-
-inline int check_launch(const char* what) {
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return bcos_set_hip_error(what, err);
-    return BCOS_OK;
-}
 
 // v[n, r, :] = sum_j a_j * w[cls[n, j], :],  a_j = ((coef * scale[n, r, cls[n, j]]) * row_scale[n r]) * c[n, j]  -- the factors of
 // head_rank1_kernel in its order, the functional's coefficient last, so that J = 1 with c = 1 gives its bits.  The sum is ONE fp32 chain in
@@ -144,8 +137,6 @@ inline unsigned head_grid(int64_t rows) {
     if (blocks > MAX_HEAD_BLOCKS) blocks = MAX_HEAD_BLOCKS;
     return (unsigned)blocks;
 }
-
-inline bool misaligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
 
 }  // namespace
 

@@ -2,11 +2,19 @@
 #ifndef BCOS_INTERNAL_H
 #define BCOS_INTERNAL_H
 #include <hip/hip_runtime.h>
+#include "bcos_hip.h"
 
 // record an error for bcos_last_error_string() and return `code`
 int bcos_set_error(int code, const char* msg);
 // record a HIP runtime error; returns BCOS_E_LAUNCH
 int bcos_set_hip_error(const char* what, hipError_t err);
+// behind a kernel launch: BCOS_OK, or the launch error recorded under `what`
+inline int check_launch(const char* what) {
+    const hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return bcos_set_hip_error(what, err);
+    return BCOS_OK;
+}
+inline bool misaligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
 // current value of a bcos_option (include/bcos_hip.h); `option` must be a valid enumerator
 #include <stdint.h>
 int64_t bcos_option(int option);

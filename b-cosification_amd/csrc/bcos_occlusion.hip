@@ -10,8 +10,8 @@
 #include <stdint.h>
 #include "bcos_hip.h"
 #include "bcos_internal.h"
+#include "bcos_f16x2.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
@@ -199,12 +199,6 @@ __global__ __launch_bounds__(TPB) void occlusion_accumulate_kernel(const float* 
                 if (t0 + k < T) out[((int64_t)(t0 + k) * H + h) * W + w] = acc[k];
         }
     }
-}
-
-inline int check_launch(const char* what) {
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return bcos_set_hip_error(what, err);
-    return BCOS_OK;
 }
 
 }  // namespace

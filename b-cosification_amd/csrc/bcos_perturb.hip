@@ -11,8 +11,7 @@
 #include <stdint.h>
 #include "bcos_hip.h"
 #include "bcos_internal.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "bcos_f16x2.h"
 
 namespace {
 
@@ -236,17 +235,10 @@ __global__ __launch_bounds__(TPB) void class_scores_kernel(const float* __restri
         for (int d = 32; d >= 1; d >>= 1) mx = fmaxf(mx, __shfl_xor(mx, d));
         float sum = 0.f;
         for (int c = lane; c < CL; c += 64) sum += expf(row[c] - mx);
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) sum += __shfl_xor(sum, d);
+        sum = wave_sum(sum);
         res = expf(row[t] - mx) / sum;
     }
     if (lane == 0) out[r] = res;
-}
-
-inline int check_launch(const char* what) {
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return bcos_set_hip_error(what, err);
-    return BCOS_OK;
 }
 
 inline int64_t select_words(int64_t B, int64_t K) { return B * 256 + B * K * 256 + 2 * B * K; }

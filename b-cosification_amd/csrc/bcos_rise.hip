@@ -10,9 +10,9 @@
 #include <stdint.h>
 #include "bcos_hip.h"
 #include "bcos_internal.h"
+#include "bcos_f16x2.h"
 #include "bcos_rise_mask.h"      // (switches fp contraction off for this translation unit)
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
@@ -168,12 +168,6 @@ __global__ __launch_bounds__(TPB) void rise_accumulate_kernel(const float* __res
         for (int k = 0; k < TS; ++k)
             if (k < nt) out[((int64_t)(t0 + k) * H + h) * W + w] = tot[k] / fn / p1;
     }
-}
-
-inline int check_launch(const char* what) {
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return bcos_set_hip_error(what, err);
-    return BCOS_OK;
 }
 
 // what the three entry points share: 2 <= s <= 8 and image sizes whose upsampled extent 2 U stays below 2^24

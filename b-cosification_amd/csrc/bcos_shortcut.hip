@@ -9,8 +9,9 @@
 // one fma chain over the first and one over the second 16-byte piece of every step, the two added, then the two halves of the wave) and the
 // forward epilogue expressions in the order of bcos_tapconv.hip's specialised kinds ([RELU |] [SCALE_OUT |] [ADDEND]).  That file is
 // compiled with the compiler's default contraction of a * b + c into one fma; this one switches contraction off and writes the two fused
-// operations of the epilogue (the bias stage and the channel affine) as explicit fmas.  split4_f16, the scale rule and the epilogue are
-// restated here; they must stay what bcos_tapconv.hip has.
+// operations of the epilogue (the bias stage and the channel affine) as explicit fmas.  The split, the scale rule and the lane-group maximum are the
+// definitions both files share (bcos_f16x2.h); what is restated here is the order of the epilogue expressions (and the patch norm's
+// summation order) and nothing else.
 //
 // Shape: 256 threads = 2 x 2 waves, one 64-row tile per workgroup and 256 output columns at a time (C4 = 512: two passes, the small A
 // operands re-read from L2): a wave owns 32 rows x 128 columns = 4 accumulator tiles.
@@ -28,11 +29,7 @@
 #include <stdint.h>
 #include "bcos_hip.h"
 #include "bcos_internal.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+#include "bcos_f16x2.h"
 
 namespace {
 
@@ -48,51 +45,6 @@ struct SArgs {
     int M, PQ, Q, H, W, stride;
     unsigned lsb;
 };
-
-// max over the 32 lanes of each half of a wave on the vector ALU (DPP); lanes 16 and 48 hold the result (bcos_tapconv.hip: group_max_u32<32>)
-__device__ __forceinline__ unsigned half_max_u32(unsigned v) {
-    v = max(v, (unsigned)__builtin_amdgcn_update_dpp((int)v, (int)v, 0xB1, 0xF, 0xF, false));       // quad_perm [1,0,3,2]
-    v = max(v, (unsigned)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x4E, 0xF, 0xF, false));       // quad_perm [2,3,0,1]
-    v = max(v, (unsigned)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x141, 0xF, 0xF, false));      // row_half_mirror
-    v = max(v, (unsigned)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x140, 0xF, 0xF, false));      // row_mirror
-    v = max(v, (unsigned)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x142, 0xA, 0xF, false));      // row_bcast15 into rows 1 and 3
-    return v;
-}
-
-// four fp32 values -> (h, l) f16 pairs with h = f16(x s), l = f16(x s - h): the instructions of bcos_tapconv.hip's split4_f16<false>
-__device__ __forceinline__ void split4_f16(const f32x4& x, const float s, unsigned& h01, unsigned& h23, unsigned& l01, unsigned& l23) {
-    unsigned a, b, c, d;
-    asm("v_fma_mixlo_f16 %0, %4, %8, 0\n\t"
-        "v_fma_mixlo_f16 %1, %6, %8, 0\n\t"
-        "v_fma_mixhi_f16 %0, %5, %8, 0\n\t"
-        "v_fma_mixhi_f16 %1, %7, %8, 0\n\t"
-        "v_fma_mixlo_f16 %2, %4, %8, -%0 op_sel_hi:[0,0,1]\n\t"
-        "v_fma_mixlo_f16 %3, %6, %8, -%1 op_sel_hi:[0,0,1]\n\t"
-        "v_fma_mixhi_f16 %2, %5, %8, -%0 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\t"
-        "v_fma_mixhi_f16 %3, %7, %8, -%1 op_sel:[0,0,1] op_sel_hi:[0,0,1]"
-        : "=&v"(a), "=&v"(b), "=&v"(c), "=&v"(d)
-        : "v"(x[0]), "v"(x[1]), "v"(x[2]), "v"(x[3]), "v"(s));
-    h01 = a; h23 = b; l01 = c; l23 = d;
-}
-
-// the eight k of a lane's fragment (two 16-byte pieces) -> its h and l fragments
-__device__ __forceinline__ void split_frag(const f32x4& x0, const f32x4& x1, const float s, f16x8& h, f16x8& l) {
-    unsigned h01, h23, h45, h67, l01, l23, l45, l67;
-    split4_f16(x0, s, h01, h23, l01, l23);
-    split4_f16(x1, s, h45, h67, l45, l67);
-    h = __builtin_bit_cast(f16x8, u32x4{h01, h23, h45, h67});
-    l = __builtin_bit_cast(f16x8, u32x4{l01, l23, l45, l67});
-}
-
-// operand scale of a row from the bit pattern of its max |A|: max * scale in [2^14, 2^15); and the inverse of such a scale
-__device__ __forceinline__ float row_scale_of(unsigned maxbits) {
-    unsigned E = maxbits >> 23;
-    E = E < 15u ? 15u : E;
-    return __uint_as_float((268u - E) << 23);
-}
-__device__ __forceinline__ float inv_scale(float s) { return __uint_as_float((254u - (__float_as_uint(s) >> 23)) << 23); }
-
-__device__ __forceinline__ unsigned absbits(float v) { return __float_as_uint(v) & 0x7fffffffu; }
 
 // One [32 x 16 NK] x [16 NK x 128] contraction of a wave: the A fragments of row `a_off` (byte offset of the lane's first piece: row base +
 // 32 bytes for the upper half of the wave) through descriptor `ra`, split with the row's scale `sc`; the weight image `wb` (already at the
@@ -253,7 +205,7 @@ __global__ __launch_bounds__(NT, 2) void shortcut_conv3_kernel(const SArgs p) {
                 }
                 if (want_max) {
                     // the row's maximum over this wave's 128 columns; over the column passes in LDS (the same lane owns the word in every pass)
-                    const unsigned a = half_max_u32(mx);
+                    const unsigned a = group_max_u32<32>(mx);
                     if (frow == 16) {
                         unsigned* w = sMax + wn * BM + wm * 32 + lrow;
                         *w = part == 0 ? a : max(*w, a);

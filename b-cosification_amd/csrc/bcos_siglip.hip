@@ -17,6 +17,7 @@
 #include <stdint.h>
 #include "bcos_hip.h"
 #include "bcos_internal.h"
+#include "bcos_f16x2.h"
 
 namespace {
 
@@ -49,13 +50,6 @@ struct SiglipArgs {
     float* part;             // [3, N]   per batch row: sum logsigmoid, sum G q, sum G
     int L, N, M, D, pos_offset, p, normalize, detach_pow;
 };
-
-// the butterfly whose partners add the same two values: every lane ends with the same bits
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 // max(||x||, eps) from the sum of squares.  A row below the clamp gets it with a minus sign: the workspace carries that to the gradient
 // pass, where such a row's norm is a constant (torch's clamp_min passes no gradient there).  Every normalised element is x / norm, an

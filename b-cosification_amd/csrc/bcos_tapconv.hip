@@ -29,9 +29,7 @@
 #include <type_traits>
 #include "bcos_hip.h"
 #include "bcos_internal.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+#include "bcos_f16x2.h"
 
 
 namespace {
@@ -117,22 +115,6 @@ __device__ __forceinline__ bool tile_row_nij(const P& p, int m0, int r, int& n, 
     jj = rem - i * p.g.Q;
     return true;
 }
-
-// max over groups of G consecutive lanes (G = 8, 16, 32; groups aligned to G) on the vector ALU (DPP), no LDS traffic.
-// After the call the lanes with (lane % G) == group_max_lane<G>() hold the group's max.
-template <int G>
-__device__ __forceinline__ unsigned group_max_u32(unsigned v) {
-    static_assert(G == 8 || G == 16 || G == 32, "group size");
-    auto dpp = [](unsigned x, auto ctrl) { return (unsigned)__builtin_amdgcn_update_dpp((int)x, (int)x, decltype(ctrl)::value, 0xF, 0xF, false); };
-    v = max(v, dpp(v, std::integral_constant<int, 0xB1>{}));       // quad_perm [1,0,3,2]
-    v = max(v, dpp(v, std::integral_constant<int, 0x4E>{}));       // quad_perm [2,3,0,1]
-    v = max(v, dpp(v, std::integral_constant<int, 0x141>{}));      // row_half_mirror: 8 lanes agree
-    if (G >= 16) v = max(v, dpp(v, std::integral_constant<int, 0x140>{}));   // row_mirror: 16 lanes agree
-    if (G == 32)                                                    // row_bcast15 into rows 1 and 3: lanes 16..31 of each half
-        v = max(v, (unsigned)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x142, 0xA, 0xF, false));
-    return v;
-}
-template <int G> constexpr int group_max_lane() { return G == 32 ? 16 : 0; }
 
 // column parts of an epilogue: 192 -> 3 x 64, 256 -> 2 x 128; EPI_SPLIT_128 (development switch): 128 -> 2 x 64, which halves the
 // transpose buffer (35 instead of 68 KB) so that three 128 x 128 workgroups fit a CU's LDS
@@ -339,15 +321,6 @@ __device__ __forceinline__ void epi_part_generic(float* smem, const int pm, cons
             if (e.mul_csh) mcsh4[q] = e.mul_csh[c];
         }
     }
-    // `mul` given as the kept ACTIVATION a = relu(lin s csc + csh) of the layer below (B = 2, s = |lin| / norm) instead of its
-    // stored multiplier t = s csc gate: |lin|^2 = |a - csh| norm / |csc|, so t = csc sqrt(|a - csh| / (|csc| norm)) where a > 0
-    auto rebuild_t = [&](float a, float nrm, float csc, float csh) {
-        const float z = fabsf(a - csh);
-        const float den = fabsf(csc) * nrm;
-        // hardware reciprocal / square root (1 ulp each): the IEEE division + sqrt sequences are ~20 instructions per
-        // element in an epilogue that is issue-bound, and t enters a product whose other factor carries fp32 rounding anyway
-        return (a > 0.f && den > 0.f) ? csc * __builtin_amdgcn_sqrtf(z * __builtin_amdgcn_rcpf(den)) : 0.f;
-    };
     // subsampled addend (bcos_epilogue.addend_sub = s > 1, gradient launches only): the addend tensor holds the pixels
     // (h % s == 0, w % s == 0) alone; epi_rows_generic left each row's pixel index in it (or -1) where forward launches keep
     // their patch norms
@@ -440,7 +413,7 @@ __device__ __forceinline__ void epi_part_generic(float* smem, const int pm, cons
                 if (mul_from_act) {
                     const float mn = e.mul_norm[ok[u] ? pix : 0];
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) m1[u][q] = rebuild_t(m1[u][q], mn, mcsc4[q], mcsh4[q]);
+                    for (int q = 0; q < 4; ++q) m1[u][q] = bcos_mul_from_act(m1[u][q], mn, mcsc4[q], mcsh4[q]);
                 }
                 m2[u] = e.mul2 ? *reinterpret_cast<const f32x4*>(e.mul2 + idx[u]) : zero4;
                 g2[u] = e.gate2 ? *reinterpret_cast<const f32x4*>(e.gate2 + idx[u]) : zero4;
@@ -531,7 +504,7 @@ __device__ __forceinline__ void epi_part_generic(float* smem, const int pm, cons
                         s *= gate;
                         v *= gate;
                     }
-                    const float o1 = e.mul ? v * (mul_from_act ? rebuild_t(e.mul[idx], e.mul_norm[pix], mcsc4[q], mcsh4[q]) : e.mul[idx]) : v;
+                    const float o1 = e.mul ? v * (mul_from_act ? bcos_mul_from_act(e.mul[idx], e.mul_norm[pix], mcsc4[q], mcsh4[q]) : e.mul[idx]) : v;
                     if (e.out) e.out[idx] = o1;
                     mx1[u] = max(mx1[u], __float_as_uint(o1) & 0x7fffffffu);
                     if (e.out2) {
@@ -601,8 +574,6 @@ __device__ __forceinline__ float mul_then_add(float a, float b, float c) {
     const float prod = a * b;
     return prod + c;
 }
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 template <int BM, int BN, int WAVES_M, int WAVES_N, bool NORM, bool SCALED, int NT, bool ROWX = true>
 __device__ __forceinline__ void epi_rows_fast(float* smem, const float* ss, const float* ROWSS, const float* AINV, const int m0,
@@ -739,10 +710,6 @@ __device__ __forceinline__ void epi_part_fast(float* smem, const int pm, const i
     auto stq_sc = [](const __amdgpu_buffer_rsrc_t& r, unsigned voff, const f32x4& v) {
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, (int)voff, 0, AUX_SC);
     };
-    auto absmax4 = [](const f32x4& o) {
-        return max(max(__float_as_uint(o[0]) & 0x7fffffffu, __float_as_uint(o[1]) & 0x7fffffffu),
-                   max(__float_as_uint(o[2]) & 0x7fffffffu, __float_as_uint(o[3]) & 0x7fffffffu));
-    };
     constexpr int CPR = SBN / 4;
     constexpr int RPP = NT / CPR;
     constexpr int PASSES = SBM / RPP;
@@ -837,7 +804,8 @@ __device__ __forceinline__ void epi_part_fast(float* smem, const int pm, const i
                     val[q] *= gate;
                 }
             }
-            if (MULACT) {          // t = csc sqrt(|a - csh| / (|csc| norm)) where the kept activation a is positive (B = 2, no residual)
+            if (MULACT) {          // `mul` holds the kept activation (B = 2, no residual): bcos_mul_from_act (bcos_f16x2.h) written out -- through the
+                                   // call the compiler packs the four lanes' products differently (same bits, other instructions)
                 const float mn = e.mul_norm[rw[u].pix >= 0 ? rw[u].pix : 0];
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
@@ -848,7 +816,7 @@ __device__ __forceinline__ void epi_part_fast(float* smem, const int pm, const i
             }
             const f32x4 o1 = MUL ? val * m1[u] : val;
             stq(r_out, voff[u], o1);
-            mx1[u] = want_max1 ? absmax4(o1) : 0u;
+            mx1[u] = want_max1 ? absbits4(o1) : 0u;
             if (OUT2) {
                 f32x4 o2 = val;
                 if (MUL2) o2 *= m2[u];
@@ -857,7 +825,7 @@ __device__ __forceinline__ void epi_part_fast(float* smem, const int pm, const i
                     for (int q = 0; q < 4; ++q) o2[q] = (__float_as_uint(m1[u][q]) & 1u) ? o2[q] : 0.f;
                 }
                 stq(r_out2, voff[u], o2);
-                mx2[u] = want_max2 ? absmax4(o2) : 0u;
+                mx2[u] = want_max2 ? absbits4(o2) : 0u;
             }
             if (SCALE_OUT) stq_sc(r_sc, voff[u], s);
         }
@@ -1490,8 +1458,6 @@ BCOS_DEV_SWITCH(H2_KO, 0);
 #ifndef H2_PIPE_SMALL
 #define H2_PIPE_SMALL 2           // pipeline of the <= 4-accumulator tiles: 2 = one 16-k step per barrier, 3 = two
 #endif
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
 #ifndef H2_PRIO
 #define H2_PRIO 0                 // wave priority of the split-f16 main loops (s_setprio): 0 = never raised, 1 = raised around the matrix instructions of a step,
                                   // 2 = raised for the whole K loop (prologue and epilogue at priority 0: the other workgroup of the CU is usually in one of them)
@@ -1499,52 +1465,7 @@ typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
 #ifndef H2_MIX_SPLIT
 #define H2_MIX_SPLIT 1            // 1 = the (h, l) split as two v_fma_mix{lo,hi}_f16 per element (split4_f16), 0 = the scalar expressions left to the compiler (rounds 2-5); same bits
 #endif
-// (h, l) f16 split of fp32 values times a power of two `s`, two values into the two halves of one register each:
-//   h = f16(x s),  l = f16(x s - h).
-// x s and x s - h are exact in fp32 (s is a power of two, h holds the leading 11 bits of x s), so each result is rounded ONCE, to f16
-// -- bit for bit what (_Float16)(x * s) and (_Float16)(x * s - (float)h) give.  Written as the instructions themselves: v_fma_mixlo_f16 /
-// v_fma_mixhi_f16 take fp32 (or, per source, f16-half) operands, compute the fma in fp32 and write the f16 result into the low / high
-// half of the destination -- two vector instructions per element and no packing.  Left to the compiler the same expressions become
-// multiply / convert / convert back / subtract / convert / pack over register PAIRS (v_pk_mul_f32, v_pk_fma_f32 ...: ~6 instructions
-// per element plus the moves that build the pairs, and packed fp32 instructions beside matrix instructions cost more than their issue slot).
-// One 16-byte piece (four fp32 values) -> two registers of h halves and two of l halves; SUMSQ: acc += x^2 of the four values (one
-// v_fmac_f32 each: the compiler pairs neighbouring chains into v_pk_fma_f32 behind two moves).  ONE asm statement, so that nothing is
-// padded between its instructions; inside it every instruction that reads a register half written by a v_fma_mix{lo,hi}_f16 is at
-// least two instructions behind that write (gfx940+: a result written with a destination half-select needs one wait state before a
-// vector instruction reads it).
-template <bool SUMSQ>
-__device__ __forceinline__ void split4_f16(const f32x4& x, const float s, unsigned& h01, unsigned& h23, unsigned& l01, unsigned& l23, float& acc) {
-    unsigned a, b, c, d;
-    if constexpr (SUMSQ) {
-        asm("v_fma_mixlo_f16 %0, %5, %9, 0\n\t"
-            "v_fma_mixlo_f16 %1, %7, %9, 0\n\t"
-            "v_fma_mixhi_f16 %0, %6, %9, 0\n\t"
-            "v_fma_mixhi_f16 %1, %8, %9, 0\n\t"
-            "v_fmac_f32 %4, %5, %5\n\t"
-            "v_fma_mixlo_f16 %2, %5, %9, -%0 op_sel_hi:[0,0,1]\n\t"
-            "v_fma_mixlo_f16 %3, %7, %9, -%1 op_sel_hi:[0,0,1]\n\t"
-            "v_fmac_f32 %4, %6, %6\n\t"
-            "v_fma_mixhi_f16 %2, %6, %9, -%0 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\t"
-            "v_fmac_f32 %4, %7, %7\n\t"
-            "v_fma_mixhi_f16 %3, %8, %9, -%1 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\t"
-            "v_fmac_f32 %4, %8, %8"
-            : "=&v"(a), "=&v"(b), "=&v"(c), "=&v"(d), "+v"(acc)
-            : "v"(x[0]), "v"(x[1]), "v"(x[2]), "v"(x[3]), "v"(s));
-    } else {
-        asm("v_fma_mixlo_f16 %0, %4, %8, 0\n\t"
-            "v_fma_mixlo_f16 %1, %6, %8, 0\n\t"
-            "v_fma_mixhi_f16 %0, %5, %8, 0\n\t"
-            "v_fma_mixhi_f16 %1, %7, %8, 0\n\t"
-            "v_fma_mixlo_f16 %2, %4, %8, -%0 op_sel_hi:[0,0,1]\n\t"
-            "v_fma_mixlo_f16 %3, %6, %8, -%1 op_sel_hi:[0,0,1]\n\t"
-            "v_fma_mixhi_f16 %2, %5, %8, -%0 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\t"
-            "v_fma_mixhi_f16 %3, %7, %8, -%1 op_sel:[0,0,1] op_sel_hi:[0,0,1]"
-            : "=&v"(a), "=&v"(b), "=&v"(c), "=&v"(d)
-            : "v"(x[0]), "v"(x[1]), "v"(x[2]), "v"(x[3]), "v"(s));
-    }
-    h01 = a; h23 = b; l01 = c; l23 = d;
-}
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+// (the (h, l) split itself: split4_f16, bcos_f16x2.h)
 
 // pipeline of a split-f16 tile: 1 for the 8-accumulator tiles, H2_PIPE_SMALL otherwise -- except the 32-column gradient tiles
 // (the depth-to-space stem gradient: 3 matrix instructions per 16-k step and wave), which take two sub-steps per barrier
@@ -1628,10 +1549,9 @@ __device__ __forceinline__ void tile_body_h2(const KArgs& p, float* smem, const 
             unsigned v = rmax[j];
             v = max(v, (unsigned)__shfl_xor((int)v, 1));
             v = max(v, (unsigned)__shfl_xor((int)v, 2));
-            unsigned E = v >> 23;                  // biased exponent of the row max (the bit patterns carry no sign)
-            E = E < 15u ? 15u : E;
-            a_scale[j] = __uint_as_float((268u - E) << 23);     // max * scale in [2^14, 2^15)
-            a_inv[j] = __uint_as_float((E - 14u) << 23);
+            const unsigned E = f16x2_exp(v);       // of the row max
+            a_scale[j] = f16x2_scale(E);           // max * scale in [2^14, 2^15)
+            a_inv[j] = f16x2_inv(E);
         }
     }
 
@@ -2236,9 +2156,7 @@ __device__ __forceinline__ void tile_body_d(const KArgs& p, float* smem, const i
             unsigned v = rmax[j];
             v = max(v, (unsigned)__shfl_xor((int)v, 1));
             v = max(v, (unsigned)__shfl_xor((int)v, 2));
-            unsigned E = v >> 23;                  // biased exponent of the row max (the bit patterns carry no sign)
-            E = E < 15u ? 15u : E;
-            rsc[j] = __uint_as_float((268u - E) << 23);                                          // max * scale in [2^14, 2^15)
+            rsc[j] = row_scale_of(v);              // from the row max: max * scale in [2^14, 2^15)
             if ((lane & 3) == 0) s_scale[r0 + 16 * j] = rsc[j];
         }
     }
@@ -2297,7 +2215,7 @@ __device__ __forceinline__ void tile_body_d(const KArgs& p, float* smem, const i
     auto split_slice = [&](auto slice_c, const f32x4 (&x0)[TM], const f32x4 (&x1)[TM]) {
         constexpr int SL = decltype(slice_c)::value;
         constexpr int i = SL / 2, piece = SL & 1;
-        u32x4v h4 = __builtin_bit_cast(u32x4v, af[0][i]), l4 = __builtin_bit_cast(u32x4v, af[1][i]);
+        u32x4 h4 = __builtin_bit_cast(u32x4, af[0][i]), l4 = __builtin_bit_cast(u32x4, af[1][i]);
         unsigned h01, h23, l01, l23;
         split4_f16<NORM>(piece ? x1[i] : x0[i], f_scale[i], h01, h23, l01, l23, piece ? pb[i] : pa[i]);
         h4[piece * 2] = h01; h4[piece * 2 + 1] = h23;
@@ -2517,7 +2435,7 @@ __device__ __forceinline__ void tile_body_d(const KArgs& p, float* smem, const i
     float a_inv[BM / (NT / 4)];      // inverse row scales in staging layout (what tile_epilogue takes): 2^-e from the row's 2^e
 #pragma unroll
     for (int j = 0; j < BM / (NT / 4); ++j)
-        a_inv[j] = __uint_as_float((254u - (__float_as_uint(s_scale[(tid >> 2) + (NT / 4) * j]) >> 23)) << 23);
+        a_inv[j] = inv_scale(s_scale[(tid >> 2) + (NT / 4) * j]);
     __syncthreads();                           // (the epilogue's row records may overlap the scale table)
     float ss[TM];
 #pragma unroll
@@ -2831,18 +2749,16 @@ __device__ __forceinline__ void tile_body_p(const PT& p, float* smem, const int 
         }
         if (jr >= 0) {
             base = (jr << 16) | ((jc + jr * rotq) & cmask);
-            unsigned E = s_imgmax[(n - n_first) & 15] >> 23;
-            E = E < 15u ? 15u : E;
+            unsigned E = f16x2_exp(s_imgmax[(n - n_first) & 15]);
             E -= (unsigned)(pass * LVL_STEP);      // (>= 15: a level never exceeds (E - 15) / LVL_STEP)
-            inv = __uint_as_float((E - 14u) << 23);
+            inv = f16x2_inv(E);
         }
         s_base[r] = base;
         s_rowinv[r] = inv;
     }
     if (tid < 16) {
-        unsigned E = s_imgmax[tid] >> 23;          // biased exponent of the image max (the bit patterns carry no sign)
-        E = E < 15u ? 15u : E;
-        const unsigned Es = 268u - E + (unsigned)(pass * LVL_STEP);
+        const unsigned E = f16x2_exp(s_imgmax[tid]);          // of the image max
+        const unsigned Es = f16x2_scale_bexp(E) + (unsigned)(pass * LVL_STEP);
         s_imgscale[tid] = __uint_as_float((Es > 254u ? 254u : Es) << 23);       // max * scale in [2^14, 2^15) at level 0
     }
     lds_barrier();
@@ -2857,7 +2773,7 @@ __device__ __forceinline__ void tile_body_p(const PT& p, float* smem, const int 
         constexpr int it = decltype(it_c)::value;
 #if H2_MIX_SPLIT
         if (!clamp_h) {            // (uniform; level 0, i.e. every pass of an image without the ladder: two instructions per element, see split4_f16)
-            u32x4v h4, l4;
+            u32x4 h4, l4;
             unsigned h01, h23, l01, l23;
             split4_f16<NORM>(xr[it][0], isc[it], h01, h23, l01, l23, pss[it]);
             h4[0] = h01; h4[1] = h23; l4[0] = l01; l4[1] = l23;
@@ -3505,12 +3421,9 @@ __global__ __launch_bounds__(256) void weight_rowscale_kernel(const float* __res
     if (row >= rows_pad) return;
     unsigned m = 0u;
     if (row < rows)
-        for (int k = lane; k < Ktot; k += 64) m = max(m, __float_as_uint(wt[(int64_t)row * Ktot + k]) & 0x7fffffffu);
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o));
-    unsigned E = m >> 23;
-    E = E < 15u ? 15u : E;
-    if (lane == 0) cinv[row] = __uint_as_float((E - 14u) << 23);
+        for (int k = lane; k < Ktot; k += 64) m = max(m, absbits(wt[(int64_t)row * Ktot + k]));
+    m = wave_max_u32(m);
+    if (lane == 0) cinv[row] = f16x2_inv(f16x2_exp(m));
 }
 
 __global__ __launch_bounds__(256) void split_weights_h2_kernel(const float* __restrict__ wt, uint4* __restrict__ wt2,
@@ -3569,9 +3482,7 @@ __global__ __launch_bounds__(256) void split_weights_h2_fused_kernel(const float
     }
     __syncthreads();
     if (tid < 32) {
-        unsigned E = s_max[tid] >> 23;
-        E = E < 15u ? 15u : E;
-        const float ci = __uint_as_float((E - 14u) << 23);
+        const float ci = f16x2_inv(f16x2_exp(s_max[tid]));
         if (blockIdx.y == 0) cinv[row0 + tid] = ci;
         s_scale[tid] = 1.0f / ci;                                     // exact: a power of two
     }
@@ -3682,9 +3593,7 @@ __global__ __launch_bounds__(256) void weight_prep_gather_kernel(const bcos_weig
             for (int u = 0; u < 8; ++u) {
                 if (r0 + u < live) {            // (uniform over the workgroup)
                     if (k < k_hi) bank[(int64_t)(row0 + r0 + u) * Ktot + k] = v[u];
-                    unsigned m = k < k_hi ? __float_as_uint(v[u]) & 0x7fffffffu : 0u;
-#pragma unroll
-                    for (int o = 32; o >= 1; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o));
+                    const unsigned m = wave_max_u32(k < k_hi ? absbits(v[u]) : 0u);
                     if ((tid & 63) == 0 && m) atomicMax(row_max + jb.row_offset + row0 + r0 + u, m);
                 }
             }
@@ -3707,9 +3616,7 @@ __global__ __launch_bounds__(256) void weight_prep_split_kernel(const bcos_weigh
     if (tile >= tiles) return;
     const int tid = threadIdx.x, lane = tid & 63;
     const int row = tile * 32 + (lane & 31);
-    unsigned E = (row < rows ? row_max[jb.row_offset + row] : 0u) >> 23;
-    E = E < 15u ? 15u : E;
-    const float ci = __uint_as_float((E - 14u) << 23);
+    const float ci = f16x2_inv(f16x2_exp(row < rows ? row_max[jb.row_offset + row] : 0u));
     const float scale = 1.0f / ci;                                // exact: a power of two
     uint4* wt2 = reinterpret_cast<uint4*>(jb.image);
     if (kgroup == 0 && tid < 32) reinterpret_cast<float*>(static_cast<char*>(jb.image) + h2_image_bytes(rows, Ktot))[tile * 32 + tid] = ci;

@@ -16,17 +16,9 @@
 #include <type_traits>
 #include "bcos_hip.h"
 #include "bcos_internal.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+#include "bcos_f16x2.h"
 
 namespace {
-
-inline int check_launch(const char* what) {
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return bcos_set_hip_error(what, err);
-    return BCOS_OK;
-}
 
 // ---- dy/dlin and dL/dnorm of one output pixel: one wavefront per row (grid-stride) ---------------------------------------
 // General form: s = c^(B-1), c = q + 1e-6, q = |lin| / norm.  q is rebuilt from lin = y / s (s > 0 in this form) rather than
@@ -169,8 +161,7 @@ __global__ __launch_bounds__(256) void patch_norm_bwd_kernel(const float* __rest
             if (i < P && j < Q) t += r[((int64_t)n * P + i) * Q + j];
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o);
+    t = wave_sum(t);
     const float* src = x + pix * x_pitch;
     float* dst = out + pix * C;
     const float* ad = add ? add + pix * C : nullptr;          // (bcos_patch_norm_bwd_add: a gradient that reaches the same tensor by another path)
@@ -252,7 +243,6 @@ constexpr int WG_K = 32;           // pixels per stage
 constexpr int WG_LD = WG_T + 4;    // LDS row pitch (floats): rows of different pixels start in different banks
 
 typedef __bf16 wg_bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned wg_u32x4 __attribute__((ext_vector_type(4)));
 
 // X3 = true (round 5): the products run on the bf16 matrix pipe over EXACT 3-way splits of both operands, x = h + m + l (8 + 8 + 8
 // significand bits, fp32's exponent range: no scaling), a b = a_h b_h + (a_h b_m + a_m b_h) + (a_m b_m + a_h b_l + a_l b_h): six
@@ -355,7 +345,7 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const WgradArgs p) {
                         const float r2 = r1 - __uint_as_float(mu);
                         hh[q] = hu; mm[q] = mu; ll[q] = __float_as_uint(r2);
                     }
-                    wg_u32x4 ph, pm, pl;
+                    u32x4 ph, pm, pl;
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
                         ph[q] = hh[2 * q + 1] | (hh[2 * q] >> 16);

@@ -13,36 +13,13 @@
 #include <atomic>
 #include "bcos_hip.h"
 #include "bcos_internal.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "bcos_f16x2.h"
 
 namespace {
 
 constexpr int TPB = 256;
 
-inline int check_launch(const char* what) {
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return bcos_set_hip_error(what, err);
-    return BCOS_OK;
-}
-
-__device__ inline float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // ---- LayerNorm over the last dimension, one wavefront per row -----------------------------------------------
-__device__ inline unsigned wave_max_u32(unsigned v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = max(v, (unsigned)__shfl_xor((int)v, o));
-    return v;
-}
-__device__ inline unsigned abs_bits4(const f32x4 v) {
-    return max(max(__float_as_uint(v[0]) & 0x7fffffffu, __float_as_uint(v[1]) & 0x7fffffffu),
-               max(__float_as_uint(v[2]) & 0x7fffffffu, __float_as_uint(v[3]) & 0x7fffffffu));
-}
-
 // Rows of up to 256 floats (D % 4 == 0): the row lives in ONE float4 per lane -- read once, two wavefront reductions, written
 // once, 16-byte accesses -- and the row's max |y| (what the split-f16 contraction reading y scales its operand by) falls out
 // of the registers.  Other widths take the strided loop.
@@ -72,7 +49,7 @@ __global__ __launch_bounds__(TPB) void layernorm_fwd_kernel(const float* __restr
             if (on) *reinterpret_cast<f32x4*>(y + r * D + lane * 4) = o;
             if (rstd_out && lane == 0) rstd_out[r] = 1.0f / sd;
             if (absmax_out) {
-                const unsigned m = wave_max_u32(on ? abs_bits4(o) : 0u);
+                const unsigned m = wave_max_u32(on ? absbits4(o) : 0u);
                 if (lane == 0) absmax_out[r] = m;
             }
         }
@@ -177,7 +154,7 @@ __global__ __launch_bounds__(TPB) void layernorm_stats16_kernel(const float* __r
         for (int i = 0; i < NV; ++i) {
             v[i] = (live && on[i]) ? *reinterpret_cast<const f32x4*>(x + r * D + (sub + 16 * i) * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
             s += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
-            m = max(m, abs_bits4(v[i]));
+            m = max(m, absbits4(v[i]));
         }
         const float mean = sum16(s) / (float)D;
         float q = 0.f;
@@ -240,7 +217,7 @@ __global__ __launch_bounds__(TPB) void layernorm_bwd_detached_kernel(const float
             if (on && out) *reinterpret_cast<f32x4*>(out + off) = o;
             if (on && out2) *reinterpret_cast<f32x4*>(out2 + off) = o2;
             if (absmax2_out) {
-                const unsigned m = wave_max_u32(on ? abs_bits4(o2) : 0u);
+                const unsigned m = wave_max_u32(on ? absbits4(o2) : 0u);
                 if (lane == 0) absmax2_out[r] = m;
             }
         }
@@ -309,8 +286,6 @@ __global__ __launch_bounds__(TPB) void add_rows_bcast_kernel(float* __restrict__
 // Both LDS layouts are padded so that every ds_read_b128 of a 16-lane group hits 16 distinct bank quads.
 constexpr int DH = 64;
 constexpr int AT_XLD = DH + 4;      // floats per X row in LDS
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // 8 wavefronts per workgroup: the 7 column tiles of a 196-token sequence run in one round (with 4 they took two, the
 // second one quarter full); the workgroup owns the CU either way (119 KB of LDS)
@@ -437,7 +412,7 @@ __global__ __launch_bounds__(ATPB) void attention_mfma_kernel(const float* __res
                 const f32x4 vb = f32x4{o1[4 * g] * rl, o1[4 * g + 1] * rl, o1[4 * g + 2] * rl, o1[4 * g + 3] * rl};
                 *reinterpret_cast<f32x4*>(orow + 8 * g) = va;
                 *reinterpret_cast<f32x4*>(orow + 32 + 8 * g) = vb;
-                mx = max(mx, max(abs_bits4(va), abs_bits4(vb)));
+                mx = max(mx, max(absbits4(va), absbits4(vb)));
             }
             if (absmax_out) {         // max |out| of the token row over this head's 64 columns; the heads meet in one atomic max (zeroed buffer)
                 mx = max(mx, (unsigned)__shfl_xor((int)mx, 32));
@@ -463,8 +438,6 @@ __global__ __launch_bounds__(ATPB) void attention_mfma_kernel(const float* __res
 //   * the powers of two are undone exactly: per X row inside the softmax argument, per Y row in the same factor, per d at the end.
 // The k index of both contractions is stored permuted (the middle two 4-blocks of every 16 swapped) so that a lane's 8 k values
 // of one matrix instruction are one ds_read_b128 for the LDS operand and plain register order for the register operand.
-typedef _Float16 af16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 af16x4 __attribute__((ext_vector_type(4)));
 constexpr int AH_XROW = 144;        // bytes per X row and plane: 64 f16 + 16 (16 rows at distinct 16-byte bank groups)
 constexpr float AH_LOG2E = 1.4426950408889634f, AH_LN2 = 0.6931471805599453f;
 #ifndef AH_KO
@@ -477,10 +450,9 @@ BCOS_DEV_SWITCH(AH_KO, 0);
 constexpr int AH_MAXIT = 9;         // 32-row blocks of the walked operand a workgroup holds at most (288 tokens: what the LDS planes allow)
 
 __device__ __forceinline__ void split_scale_exp(unsigned maxbits, float& sc, float& inv) {
-    unsigned E = maxbits >> 23;
-    E = E < 15u ? 15u : E;
-    sc = __uint_as_float((268u - E) << 23);      // max * sc in [2^14, 2^15)
-    inv = __uint_as_float((E - 14u) << 23);
+    const unsigned E = f16x2_exp(maxbits);
+    sc = f16x2_scale(E);      // max * sc in [2^14, 2^15)
+    inv = f16x2_inv(E);
 }
 
 template <bool BWD>
@@ -538,12 +510,12 @@ __global__ __launch_bounds__(ATPB) void attention_h2_kernel(const float* __restr
             if (it < nit) {
                 const int t = (tid >> 4) + 32 * it;
                 const f32x4 xv = xreg[it], zv = zreg[it];
-                unsigned m = abs_bits4(xv);
+                unsigned m = absbits4(xv);
 #pragma unroll
                 for (int o = 8; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o));
                 float sc, inv;
                 split_scale_exp(m, sc, inv);
-                af16x4 hh, ll;
+                f16x4 hh, ll;
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     const float v = xv[q] * sc;
@@ -551,8 +523,8 @@ __global__ __launch_bounds__(ATPB) void attention_h2_kernel(const float* __restr
                     ll[q] = (_Float16)(v - (float)hh[q]);
                     zm[q] = max(zm[q], __float_as_uint(zv[q]) & 0x7fffffffu);
                 }
-                *reinterpret_cast<af16x4*>(sXh + t * AH_XROW + xpos) = hh;
-                *reinterpret_cast<af16x4*>(sXl + t * AH_XROW + xpos) = ll;
+                *reinterpret_cast<f16x4*>(sXh + t * AH_XROW + xpos) = hh;
+                *reinterpret_cast<f16x4*>(sXl + t * AH_XROW + xpos) = ll;
                 if (c4 == 0) sXinv[t] = inv;
             }
         }
@@ -605,12 +577,12 @@ __global__ __launch_bounds__(ATPB) void attention_h2_kernel(const float* __restr
         for (int g = 0; g < 8; ++g) {
             yf[g] = f32x4{0.f, 0.f, 0.f, 0.f};
             if (y < T) yf[g] = *reinterpret_cast<const f32x4*>(ysrc + (int64_t)y * 3 * inner + 8 * g + 4 * hf);
-            ym = max(ym, abs_bits4(yf[g]));
+            ym = max(ym, absbits4(yf[g]));
         }
         ym = max(ym, (unsigned)__shfl_xor((int)ym, 32));
         float ysc, yinv;
         split_scale_exp(ym, ysc, yinv);
-        af16x8 yh[4], yl[4];
+        f16x8 yh[4], yl[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j)
 #pragma unroll
@@ -638,11 +610,11 @@ __global__ __launch_bounds__(ATPB) void attention_h2_kernel(const float* __restr
             f32x16 sacc2;
 #pragma unroll
             for (int r = 0; r < 16; ++r) sacc2[r] = 0.f;
-            af16x8 ah4[4], al4[4];
+            f16x8 ah4[4], al4[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                ah4[j] = *reinterpret_cast<const af16x8*>(xh + 32 * j);
-                al4[j] = *reinterpret_cast<const af16x8*>(xl + 32 * j);
+                ah4[j] = *reinterpret_cast<const f16x8*>(xh + 32 * j);
+                al4[j] = *reinterpret_cast<const f16x8*>(xl + 32 * j);
             }
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
@@ -658,8 +630,8 @@ __global__ __launch_bounds__(ATPB) void attention_h2_kernel(const float* __restr
 #else
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const af16x8 ah = *reinterpret_cast<const af16x8*>(xh + 32 * j);
-                const af16x8 al = *reinterpret_cast<const af16x8*>(xl + 32 * j);
+                const f16x8 ah = *reinterpret_cast<const f16x8*>(xh + 32 * j);
+                const f16x8 al = *reinterpret_cast<const f16x8*>(xl + 32 * j);
                 sacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, yh[j], sacc, 0, 0, 0);
                 sacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, yl[j], sacc, 0, 0, 0);
                 sacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, yh[j], sacc, 0, 0, 0);
@@ -715,16 +687,16 @@ __global__ __launch_bounds__(ATPB) void attention_h2_kernel(const float* __restr
             const char* zl = sZl + col * zrow + (chunk * 32 + 8 * hf) * 2;
 #pragma unroll
             for (int m2 = 0; m2 < 2; ++m2) {
-                af16x8 ph, pl;
+                f16x8 ph, pl;
 #pragma unroll
                 for (int q = 0; q < 8; ++q) {
                     const float v = pr[8 * m2 + q] * 16384.0f;
                     ph[q] = (_Float16)v;
                     pl[q] = (_Float16)(v - (float)ph[q]);
                 }
-                const af16x8 zh0 = *reinterpret_cast<const af16x8*>(zh + 32 * m2), zl0 = *reinterpret_cast<const af16x8*>(zl + 32 * m2);
-                const af16x8 zh1 = *reinterpret_cast<const af16x8*>(zh + 32 * zrow + 32 * m2);
-                const af16x8 zl1 = *reinterpret_cast<const af16x8*>(zl + 32 * zrow + 32 * m2);
+                const f16x8 zh0 = *reinterpret_cast<const f16x8*>(zh + 32 * m2), zl0 = *reinterpret_cast<const f16x8*>(zl + 32 * m2);
+                const f16x8 zh1 = *reinterpret_cast<const f16x8*>(zh + 32 * zrow + 32 * m2);
+                const f16x8 zl1 = *reinterpret_cast<const f16x8*>(zl + 32 * zrow + 32 * m2);
                 o0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(zl0, ph, o0, 0, 0, 0);
                 o1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(zl1, ph, o1, 0, 0, 0);
                 o0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(zh0, pl, o0, 0, 0, 0);
@@ -745,7 +717,7 @@ __global__ __launch_bounds__(ATPB) void attention_h2_kernel(const float* __restr
                 const f32x4 vb = f32x4{o1[4 * g] * zb[0], o1[4 * g + 1] * zb[1], o1[4 * g + 2] * zb[2], o1[4 * g + 3] * zb[3]};
                 *reinterpret_cast<f32x4*>(orow + 8 * g) = va;
                 *reinterpret_cast<f32x4*>(orow + 32 + 8 * g) = vb;
-                mx = max(mx, max(abs_bits4(va), abs_bits4(vb)));
+                mx = max(mx, max(absbits4(va), absbits4(vb)));
             }
             if (absmax_out) {
                 mx = max(mx, (unsigned)__shfl_xor((int)mx, 32));

@@ -78,6 +78,15 @@ def test_default_build_is_not_a_development_build(hip_lib, tmp_path):
     assert "LOADED True" in out.stdout and "DEVELOPMENT build" in out.stderr, out.stdout + out.stderr
 
 
+def test_build_tracks_every_header():
+    """An edit of a header rebuilds the objects only if lib.build knows the header: every *.h of csrc/ and the ABI header are in lib.HEADERS."""
+    from bcos_hip import lib
+    present = {os.path.realpath(os.path.join(str(lib.CSRC), f)) for f in os.listdir(lib.CSRC) if f.endswith(".h")}
+    present.add(os.path.realpath(os.path.join(REPO, "include", "bcos_hip.h")))
+    assert "bcos_f16x2.h" in {os.path.basename(p) for p in present}
+    assert present <= {os.path.realpath(str(h)) for h in lib.HEADERS}, present
+
+
 def test_abi_argument_validation_without_gpu(hip_lib):
     """Bad arguments are rejected before any HIP call, with an errno-style code and a message."""
     from bcos_hip import lib
