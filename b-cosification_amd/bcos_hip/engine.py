@@ -65,6 +65,19 @@ def set_boundary_fusion(on):
 _SHORTCUT_FUSION_ENV = os.environ.get("BCOS_SHORTCUT_FUSION", "1") != "0"
 _SHORTCUT_FUSION = _SHORTCUT_FUSION_ENV
 SHORTCUT_FUSION_CALLS = 0
+# The stem's forward as ONE launch that reads the raw image (ops.stem_conv_fwd: the prepared [N,H,W,8] copy of the image and its maxima
+# never reach memory; same bits).  BCOS_STEM_KERNEL=0: prep_input + the tapconv launch, for A/B runs; set_stem_kernel() flips it inside a
+# process.  STEM_KERNEL_CALLS counts the fused launches issued.
+_STEM_KERNEL_ENV = os.environ.get("BCOS_STEM_KERNEL", "1") != "0"
+_STEM_KERNEL = _STEM_KERNEL_ENV
+STEM_KERNEL_CALLS = 0
+
+
+def set_stem_kernel(on=None):
+    """True / False: the fused stem launch on / off; None: back to what BCOS_STEM_KERNEL says.  Returns the previous setting."""
+    global _STEM_KERNEL
+    old, _STEM_KERNEL = _STEM_KERNEL, (_STEM_KERNEL_ENV if on is None else bool(on))
+    return old
 
 
 def set_shortcut_fusion(on):
@@ -87,6 +100,20 @@ class _DeferredShortcut:
         """the shortcut's own launch -> its output"""
         y, self.td = self.conv.fwd(self.x, relu=False, want_scale=self.want_scale, track=False)
         return y
+
+
+class _RawImage:
+    """What Conv.fwd of the stem takes in place of the prepared NHWC input where _stem_fusable allows it: the input source with the images
+    themselves and the constants of their normalisation (one fused launch that reads the raw pixels, or -- where that call is refused --
+    the source's prep launch and the stem's tapconv launch after all).  `.shape` is the NHWC shape of the prepared input that is not written."""
+
+    def __init__(self, src, mean, std):
+        self.src, self.mean, self.std = src, mean, std
+        self.shape = (src.x.shape[0], src.x.shape[2], src.x.shape[3], 8)
+
+    def prepare(self):
+        """the source's own prep launch -> the prepared input"""
+        return self.src.prepare(self.mean, self.std, True)
 
 
 def _pair(v):
@@ -198,6 +225,22 @@ class Conv:
                 if err.code != BCOS_E_NOSUP:
                     raise
                 addend = sc.run()
+        if isinstance(x, _RawImage):
+            global STEM_KERNEL_CALLS
+            raw = x
+            try:
+                y, t, _ = ops.stem_conv_fwd(raw.src.x, self.w_fwd, raw.mean, raw.std, add_inverse=raw.src.add_inverse, ch_scale=self.ch_scale,
+                                            ch_shift=self.ch_shift, relu=relu, want_scale=want_scale, flags=flags, track_absmax=track,
+                                            b=self.b, bias=self.bias)
+                STEM_KERNEL_CALLS += 1
+                self.last_gate = None
+                return y, t
+            except BcosHipError as err:
+                # (what _stem_fusable cannot see from where it stands: the call refuses before it launches anything, and prep_input and the
+                #  tapconv launch take the stem as they always did)
+                if err.code != BCOS_E_NOSUP:
+                    raise
+                x = raw.prepare()
         gate = gates.pop(0) if (relu and gates is not None) else None
         if self.max_out > 1:
             return self._fwd_maxout(x, addend, relu, want_scale, gate, flags, track)
@@ -494,12 +537,13 @@ class ResNetEngine(FusedPlan):
         """The forward pass over an input source (bcos_hip/plan.py) as a generator: it yields (nothing) behind the stem and behind every
         block, so that the passes of several sub-batches can be ISSUED interleaved (see _interleave); its return value is (head output,
         kept state)."""
-        x, xn = self._begin(src)
+        fuse_stem = _stem_fusable(self, src, gates)       # (the stem reads the raw image: no prepared copy)
+        x, xn = self._begin(src, prepare=not fuse_stem)
         gates = list(gates) if gates is not None else None
         if gates is not None and any(b.hybrid for b in self.blocks):
             raise BcosHipError("engine: replayed ReLU gates are not available for networks with a block on the nn.Module path (hybrid node)")
         st = dict(x=x, add_inverse=src.add_inverse, H=x.shape[2], W=x.shape[3], stem_ts=[], stem_hws=[], blocks=[]) if keep else None
-        a = xn
+        a = _RawImage(src, *self._consts(x.device)) if fuse_stem else xn      # (a fusable stem: its Conv.fwd issues the one launch)
         need = lambda k: k >= ops.F16X2_MIN_K      # noqa: E731  will the reader of a tensor use its per-pixel maxima?
         for si, (conv, relu) in enumerate(self.stem):
             if keep:
@@ -862,6 +906,28 @@ def _shortcut_fusable(blk, sc_in, h, gates) -> bool:
                 and _l_mode() == "f16x2" and ops.F16X2_MIN_K <= min(c3.cin, cd.cin)
                 and am_x is not None and am_x.numel() == sc_in.numel() // sc_in.shape[3]
                 and am_h is not None and am_h.numel() == N * P * Q)
+
+
+def _stem_fusable(eng, src, gates) -> bool:
+    """May ops.stem_conv_fwd stand in for ops.prep_input and the forward launch of the stem?  The network has a single 7 x 7 / stride 2 /
+    padding 3 stem convolution from the 6 (padded: 8) input channels to 64, a plain B = 2 layer (no MaxOut, no groups, no bias), its ReLU
+    (if any) decided by the value (no replayed gates, no separate gate tensor), f16x2 contraction with the pre-split image of the static
+    weight bank; the input is the plain batch of images (occluded, perturbed and RISE-prepared inputs keep their own prep launches),
+    contiguous and, like the output, below the 2 GiB of the kernel's 32-bit offsets.  On a device the native call; on CPU tensors only where
+    a test has put an emulator in its place.  (The call's own refusals are mirrored here; one that is met anyway -- BCOS_E_NOSUP -- sends
+    the stem to the pair of launches too.)"""
+    if not _STEM_KERNEL or gates is not None or _GATE_TENSOR or type(src) is not plan.Images or len(eng.stem) != 1:
+        return False
+    c, x = eng.stem[0][0], src.x
+    if not (x.is_cuda or not getattr(ops.stem_conv_fwd, "native", False)):
+        return False
+    N, H, W = x.shape[0], x.shape[2], x.shape[3]
+    P, Q = c.out_hw(H, W) if c.k == (7, 7) else (0, 0)
+    return bool(c.k == (7, 7) and c.stride == (2, 2) and c.padding == (3, 3) and c.dilation == (1, 1) and c.cin == 6 and c.cout == 64
+                and tuple(c.w_fwd.shape) == (64, 7, 7, 8) and c.max_out == 1 and c.groups == 1 and c.b == 2.0 and not c.force_pow
+                and c.bias is None and x.is_contiguous() and 0 < N <= 65535
+                and N * P * Q * 64 * 4 < 2 ** 31 and x.numel() * 4 < 2 ** 31
+                and ops.presplit_static(c.w_fwd) and _l_mode() == "f16x2")
 
 
 def _boundary_fusable(consumer, blk, rec, H, W) -> bool:

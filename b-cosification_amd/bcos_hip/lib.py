@@ -19,7 +19,7 @@ LIB_PATH = Path(os.environ["BCOS_HIP_LIB"]) if os.environ.get("BCOS_HIP_LIB") el
 CSRC = PKG_ROOT / "csrc"
 INCLUDE = REPO_ROOT / "include"
 SOURCES = ["bcos_tapconv.hip", "bcos_skinny.hip", "bcos_elementwise.hip", "bcos_vit.hip", "bcos_render.hip", "bcos_train.hip",
-           "bcos_agc.hip", "bcos_occlusion.hip", "bcos_rise.hip", "bcos_perturb.hip", "bcos_head.hip", "bcos_boundary.hip", "bcos_shortcut.hip", "bcos_dense.hip", "bcos_siglip.hip",
+           "bcos_agc.hip", "bcos_occlusion.hip", "bcos_rise.hip", "bcos_perturb.hip", "bcos_head.hip", "bcos_boundary.hip", "bcos_shortcut.hip", "bcos_stem.hip", "bcos_dense.hip", "bcos_siglip.hip",
            "bcos_abi.hip"]
 # every header a source may include -- all of csrc/*.h and the ABI header: an edit of any of them rebuilds every object
 HEADERS = sorted(CSRC.glob("*.h")) + [INCLUDE / "bcos_hip.h"]
@@ -104,6 +104,14 @@ class ShortcutConv3(C.Structure):
         "x", "x_absmax", "wd_f16x2", "csc_d", "csh_d", "td", "h", "h_absmax", "w3_f16x2", "csc_3", "csh_3", "out", "t3", "out_absmax",
         "bias_d", "bias_3", "relu_gate")] + [(n, C.c_int32) for n in (
         "N", "H", "W", "K3", "Kd", "C4", "kh", "kw", "stride", "max_out", "groups", "contraction", "flags")] + [("b", C.c_float)]
+
+
+class StemConv(C.Structure):
+    """include/bcos_hip.h: bcos_stem_conv"""
+    _fields_ = [(n, C.c_void_p) for n in (
+        "x", "mean6", "std6", "w_f16x2", "csc", "csh", "y", "t", "norm_out", "y_absmax", "x_imgmax", "x_imgmin", "bias", "relu_gate")] + [
+        (n, C.c_int32) for n in ("N", "Cx", "H", "W", "add_inverse", "Cout", "kh", "kw", "stride", "padding", "relu", "max_out", "groups",
+                                 "contraction", "flags")] + [("b", C.c_float)]
 
 
 LOOP_NAMES = ("f32", "bf16x3", "bf16x3_presplit", "f16x2_regs", "f16x2_dma", "f16x2_patch")      # include/bcos_hip.h: BCOS_LOOP_*
@@ -212,6 +220,8 @@ SIGNATURES = {
     "bcos_rise_accumulate": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P]),
     "bcos_boundary_conv3_grad": (C.c_int, [C.POINTER(BoundaryConv3), _P]),
     "bcos_shortcut_conv3_fwd": (C.c_int, [C.POINTER(ShortcutConv3), _P]),
+    "bcos_stem_conv_fwd": (C.c_int, [C.POINTER(StemConv), _P]),
+    "bcos_stem_image_range": (C.c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "bcos_perturb_select_ws_bytes": (C.c_int, [_I, _L, _I, C.POINTER(C.c_int64)]),
     "bcos_perturb_select": (C.c_int, [_P, _P, _I, _P, _P, _L, _I, _L, _I, _P]),
     "bcos_prep_input_perturbed": (C.c_int, [_P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),

@@ -673,6 +673,72 @@ def shortcut_conv3_fwd(x, wd, h, w3, *, stride=1, csc_d=None, csh_d=None, csc_3=
 shortcut_conv3_fwd.native = True       # (the engines take the fused route on CPU tensors only where a test has put an emulator in its place)
 
 
+def stem_conv_fwd(x_nchw, w, mean6, std6, *, add_inverse=False, ch_scale=None, ch_shift=None, relu=True, want_scale=False, want_norm=False,
+                  flags=0, track_absmax=None, b=2.0, bias=None, relu_gate=None, max_out=1, groups=1, contraction=None):
+    """The 7 x 7 / stride 2 stem convolution straight from the raw NCHW image in ONE launch (include/bcos_hip.h: bcos_stem_conv_fwd)
+    -> (y [N,P,Q,64], t, norm), bit for bit what
+        xn = prep_input(x_nchw, mean6, std6, cpad=8, add_inverse=add_inverse, want_absmax=True)  and
+        conv2d_fwd(xn, w, stride=(2, 2), padding=(3, 3), ch_scale=ch_scale, ch_shift=ch_shift, relu=relu, want_scale=want_scale,
+                   want_norm=want_norm, flags=flags, track_absmax=track_absmax)
+    give, without xn.  w [64,7,7,8] is the (static) forward bank.  t / norm are None unless asked for; `track_absmax`: the maxima of y, as in
+    tapconv.  Where that pair would hand its launch the per-image range of xn's maxima by a pass of bcos_image_absrange (no engine arena,
+    or images below 2048 pixels), the range is computed here from the raw image (bcos_stem_image_range) and the call follows the same
+    operand-scale rule.  BcosHipError with code BCOS_E_NOSUP for anything but this configuration on the f16x2 contraction."""
+    lib = _l.load()
+    mode = contraction if contraction is not None else (_CONTRACTION_OVERRIDE or _l.get_contraction_mode())
+    N, Cx, H, W = x_nchw.shape
+    if (mode != "f16x2" or not presplit_static(w) or tuple(w.shape) != (64, 7, 7, 8) or Cx != (3 if add_inverse else 6)
+            or any(t is not None and tuple(t.shape) != (64,) for t in (ch_scale, ch_shift))):
+        err = BcosHipError("stem_conv_fwd: needs the f16x2 contraction, a static weight bank [64,7,7,8] and a 3-channel (add_inverse) or "
+                           "6-channel image")
+        err.code = _l.BCOS_E_NOSUP
+        raise err
+    P, Q = conv_out_size(H, 7, 2, 3, 1), conv_out_size(W, 7, 2, 3, 1)
+    a = _l.StemConv()
+    a.N, a.Cx, a.H, a.W, a.add_inverse = N, Cx, H, W, int(bool(add_inverse))
+    a.Cout, a.kh, a.kw, a.stride, a.padding = int(w.shape[0]), int(w.shape[1]), int(w.shape[2]), 2, 3
+    a.relu, a.max_out, a.groups, a.flags, a.b = int(relu), int(max_out), int(groups), int(flags), float(b)
+    a.contraction = {"f32": _l.CONTRACT_F32, "bf16x3": _l.CONTRACT_BF16X3, "f16x2": _l.CONTRACT_F16X2}[mode]
+    y = torch.empty((N, P, Q, 64), device=x_nchw.device, dtype=torch.float32)
+    t = torch.empty_like(y) if want_scale else None
+    norm = torch.empty((N, P, Q), device=x_nchw.device, dtype=torch.float32) if want_norm else None
+    tensors = dict(x=x_nchw, mean6=mean6, std6=std6, csc=ch_scale, csh=ch_shift, y=y, t=t, norm_out=norm, bias=bias, relu_gate=relu_gate)
+    for k, v in tensors.items():
+        p = _dev(v, f"stem_conv_fwd.{k}")
+        setattr(a, k, p.value if p is not None else None)
+    a.w_f16x2 = _image_of(w, "_bcos_wt2_t49", lambda q: split_weights_f16x2(q, 49)).data_ptr()
+    keep = []
+    # (tapconv: a launch of 25 taps and more takes the per-image range; image_absmax hands out the plain form its LDS-DMA loop reads only
+    #  where it runs the one-workgroup-per-image pass)
+    if PATCH_LOOP and not (IMAGE_RANGE_PARTS and _ARENA is not None and H * W >= 2048):
+        rng = torch.empty(2, N, device=x_nchw.device, dtype=torch.int32)
+        _l.check(lib.bcos_stem_image_range(a.x, a.mean6, a.std6, rng[0].data_ptr(), rng[1].data_ptr(), N, Cx, H, W, a.add_inverse, _stream()),
+                 "bcos_stem_image_range")
+        a.x_imgmax, a.x_imgmin = rng[0].data_ptr(), rng[1].data_ptr()
+        keep.append(rng)
+    pixels = N * P * Q
+    am = _out_absmax(y, pixels) if (DEFAULT_TRACK_ABSMAX if track_absmax is None else track_absmax) else None
+    if am is not None:
+        a.y_absmax = am.data_ptr()
+    timing = KERNEL_TIMING
+    if timing is not None:
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        ev0.record()
+    code = lib.bcos_stem_conv_fwd(C.byref(a), _stream())
+    if timing is not None and code == 0:      # (a refused call launched nothing: the pair that takes over books its own record)
+        ev1.record()
+        # one record, as the stem's tapconv launch books it: the same algorithmic flops (K = 49 taps x 8 padded channels); bytes with the
+        # raw image in the place of the padded copy
+        epi_tensors = 1 + (t is not None)
+        nbytes = int(4 * (N * Cx * H * W + 392 * 64 + pixels * 64 * epi_tensors))
+        timing.append((ev0, ev1, 2.0 * pixels * 392 * 64, nbytes, (pixels, 392, 64)))
+    _l.check(code, "bcos_stem_conv_fwd")
+    return y, t, norm
+
+
+stem_conv_fwd.native = True            # (the engines take the fused route on CPU tensors only where a test has put an emulator in its place)
+
+
 def fwd_geom(N, H, W, Cin, Cout, kh, kw, sh, sw, ph, pw, dh=1, dw=1):
     Ho, Wo = conv_out_size(H, kh, sh, ph, dh), conv_out_size(W, kw, sw, pw, dw)
     return dict(N=N, H=H, W=W, C=Cin, P=Ho, Q=Wo, in_sh=sh, in_sw=sw, dh0=-ph, dw0=-pw, dstep_h=dh,

@@ -182,12 +182,13 @@ class FusedPlan:
         function of the image alone."""
         return passes.n_streams(x.shape[0], self._stream_limit(cotangent), x.device)
 
-    def _begin(self, src, want_absmax=True):
-        """head of every forward generator: the plan brought up to date, then -> (images, prepared NHWC input) of the source"""
+    def _begin(self, src, want_absmax=True, prepare=True):
+        """head of every forward generator: the plan brought up to date, then -> (images, prepared NHWC input) of the source
+        (`prepare` = False: None in its place -- the caller's first launch reads the images themselves)"""
         ops.require_device(src.x, type(self).__module__)
         self._ensure_fresh()
         mean, std = self._consts(src.x.device)
-        return src.x, src.prepare(mean, std, want_absmax)
+        return src.x, (src.prepare(mean, std, want_absmax) if prepare else None)
 
     def _run_forward(self, x, keep, gates=None):
         return _drive(self._run_forward_gen(Images(x), keep, gates))

@@ -1172,6 +1172,57 @@ typedef struct bcos_shortcut_conv3 {
 } bcos_shortcut_conv3;
 int bcos_shortcut_conv3_fwd(const bcos_shortcut_conv3* args, void* stream);
 
+/* -- the 7 x 7 / stride 2 stem convolution straight from the raw image (additive entry point of ABI v12) ---------------------------- */
+/* ONE launch computes what bcos_prep_input (Cpad = 8, with its per-pixel maxima) followed by the forward bcos_tapconv_ops launch of a
+ * ResNet's stem computes, without the prepared [N,H,W,8] copy of the image ever reaching memory:
+ *     xn  = ([x, 1 - x] - mean6) / std6         x [N,Cx,H,W] raw NCHW pixels; Cx = 3 with add_inverse, Cx = 6 without; two zero channels added
+ *     lin = conv(xn, W)                         7 x 7, stride 2, padding 3, 64 output channels: M = N * P * Q rows, P = (H - 1) / 2 + 1
+ *     y   = csc (lin s) + csh                   s = |lin| / sqrt(sum_k a_k^2 + 1e-6) of the row (BCOS_CONV_EPS, B = 2); relu != 0: max(y, 0)
+ *     t   = s csc (where y > 0 if relu, else 0) NULL or [M,64]; with BCOS_EPI_SCALE_GATE_LSB in `flags` an open gate also sets its low bit
+ * on the f16x2 contraction, bit for bit what the two launches give: y, t, norm_out (NULL or [M]: the patch norms) and y_absmax (NULL or
+ * [M]: per-pixel maxima of y).  w_f16x2: the image bcos_split_weights_f16x2_conv makes of the weights [64][49][8] (taps = 49, C = 8);
+ * csc / csh (NULL = 1 / 0): the folded BatchNorm, [64] each.  x_imgmax / x_imgmin (both or neither, [N]): the per-image range of the
+ * prepared input's per-pixel maxima in the form bcos_image_absrange leaves (bcos_stem_image_range computes it from the raw image) -- given
+ * them, a row of an image whose nonzero pixel maxima lie within 2^16 of the image's maximum takes that maximum as the source of its operand
+ * scale, as the tapconv launch does when it is handed bcos_operands.a_imgmax / a_imgmin; without them (or with option BCOS_OPT_PATCH = 0)
+ * every row takes the maximum over its own 49 taps, as that launch does without them.  Nothing is allocated and no device memory is read
+ * by the host.
+ * BCOS_E_INVAL: a NULL x / mean6 / std6 / y, N / H / W <= 0, Cx other than 3 (add_inverse) or 6, one of x_imgmax / x_imgmin without the
+ * other, flag bits other than BCOS_EPI_SCALE_GATE_LSB.  BCOS_E_NOSUP: anything but kh = kw = 7, stride 2, padding 3, Cout = 64, b = 2,
+ * max_out = 1, groups = 1, no bias, no replayed gate tensor, relu 0 or 1, contraction BCOS_CONTRACT_F16X2 (or the default while the
+ * process-wide mode is f16x2) with the weight image, tensors below 2 GiB, at most 65535 images, 16-byte aligned y / t / image and 4-byte
+ * aligned arrays. */
+typedef struct bcos_stem_conv {
+    const float* x;              /* [N,Cx,H,W]: the raw image                 */
+    const float* mean6;          /* [6] */
+    const float* std6;           /* [6] */
+    const void* w_f16x2;
+    const float* csc;            /* NULL or [64] */
+    const float* csh;            /* NULL or [64] */
+    float* y;                    /* [M,64] */
+    float* t;                    /* NULL or [M,64] */
+    float* norm_out;             /* NULL or [M] */
+    uint32_t* y_absmax;          /* NULL or [M] */
+    const uint32_t* x_imgmax;    /* NULL or [N] */
+    const uint32_t* x_imgmin;    /* NULL or [N] */
+    const float* bias;           /* must be NULL (BCOS_E_NOSUP) */
+    const float* relu_gate;      /* must be NULL (BCOS_E_NOSUP): replayed gates keep the pair of launches */
+    int32_t N, Cx, H, W;         /* the image's extent */
+    int32_t add_inverse;
+    int32_t Cout, kh, kw, stride, padding;
+    int32_t relu;                /* 0 none, 1 ReLU decided by the value */
+    int32_t max_out, groups;
+    int32_t contraction;         /* BCOS_CONTRACT_* */
+    int32_t flags;               /* 0 or BCOS_EPI_SCALE_GATE_LSB */
+    float b;                     /* the B-cos exponent of the layer */
+} bcos_stem_conv;
+int bcos_stem_conv_fwd(const bcos_stem_conv* args, void* stream);
+/* out_max[n] / out_min[n]: the largest / the smallest nonzero per-pixel maximum of image n of the prepared input (0xffffffff as minimum
+ * where every pixel is zero), computed from the raw image: what bcos_image_absrange gives on the maxima bcos_prep_input emits.
+ * BCOS_E_INVAL: a NULL pointer, N / H / W <= 0, Cx other than 3 (add_inverse) or 6, Cx * H * W > 2^31 - 1. */
+int bcos_stem_image_range(const float* x, const float* mean6, const float* std6, uint32_t* out_max, uint32_t* out_min, int N, int Cx,
+                          int H, int W, int add_inverse, void* stream);
+
 /* -- pixel perturbation (deletion curves; additive entry points of ABI v12) ------------------------------------------------- */
 /* An image's HW = H * W pixels are ranked by a score s (fp32, one per pixel p = h * W + w) and the first k of the ranking are REMOVED:
  * all six channels of the [r,g,b,1-r,1-g,1-b] network input are set to 0 there, as inside an Occlusion rectangle.  THE RANKING, stated
