@@ -18,7 +18,7 @@ REPO_ROOT = PKG_ROOT.parent
 LIB_PATH = Path(os.environ["BCOS_HIP_LIB"]) if os.environ.get("BCOS_HIP_LIB") else PKG_ROOT / "lib" / "libbcos_hip.so"
 CSRC = PKG_ROOT / "csrc"
 INCLUDE = REPO_ROOT / "include"
-SOURCES = ["bcos_tapconv.hip", "bcos_skinny.hip", "bcos_elementwise.hip", "bcos_vit.hip", "bcos_render.hip", "bcos_train.hip",
+SOURCES = ["bcos_tapconv.hip", "bcos_tapconv_dispatch.hip", "bcos_weights.hip", "bcos_absmax.hip", "bcos_skinny.hip", "bcos_elementwise.hip", "bcos_vit.hip", "bcos_render.hip", "bcos_train.hip",
            "bcos_agc.hip", "bcos_occlusion.hip", "bcos_rise.hip", "bcos_perturb.hip", "bcos_head.hip", "bcos_boundary.hip", "bcos_shortcut.hip", "bcos_stem.hip", "bcos_dense.hip", "bcos_siglip.hip",
            "bcos_abi.hip"]
 # every header a source may include -- all of csrc/*.h and the ABI header: an edit of any of them rebuilds every object
@@ -256,7 +256,9 @@ def build(force: bool = False, verbose: bool = False) -> Path:
             return LIB_PATH
     LIB_PATH.parent.mkdir(parents=True, exist_ok=True)
     # one object per (source, part) compiled in parallel, then one link: bcos_tapconv.hip is compiled in TAPCONV_PARTS slices
-    # (-DBCOS_TAPCONV_PART=k selects which kernel instantiations a slice carries) because its ~30 kernels dominate the build
+    # (-DBCOS_TAPCONV_PART=k selects which kernel instantiations a slice carries) because its ~30 kernels dominate the build;
+    # the slices hold tile kernels and their launchers only -- the dispatcher that routes to them is bcos_tapconv_dispatch.hip,
+    # a host-only unit, so an edit of a routing rule recompiles no kernel
     objdir = LIB_PATH.parent / "obj"
     objdir.mkdir(parents=True, exist_ok=True)
     # no -ffast-math and no -fno-hip-fp32-correctly-rounded-divide-sqrt, here or in BCOS_HIPCC_FLAGS of a product build: the rounding

@@ -30,14 +30,10 @@
 #include "bcos_hip.h"
 #include "bcos_internal.h"
 #include "bcos_f16x2.h"
+#include "bcos_tapconv_plan.h"      // KArgs, the shared constants and the launcher seam
 
 
 namespace {
-
-// process-wide DEFAULT for calls that do not choose (bcos_operands.contraction == 0): 0 = v_mfma_f32_32x32x2_f32,
-// 1 = 6 x v_mfma_f32_32x32x16_bf16 on exact 3-way splits, 2 (default) = 3 x v_mfma_f32_32x32x16_f16 on scaled 2-way splits
-// where the call provides what that needs (a_absmax + wt_f16x2), else 1
-std::atomic<int> g_contraction_mode{2};
 
 #ifndef BCOS_PHASE_TIMING
 #define BCOS_PHASE_TIMING 0       // development builds: per-workgroup clock of prologue / K loop / epilogue of tile_body_d, summed in g_phase
@@ -49,50 +45,9 @@ __device__ unsigned long long g_phase[8];          // [0..2] clock sums of prolo
 #else
 #define BCOS_PHASE_MARK(var)
 #endif
-constexpr int BK = 32;            // K floats per step
 constexpr int LDS_LD = BK + 4;    // padded LDS row (floats): 144 B, 16 rows hit 16 distinct 16-B slots
-constexpr int NTHREADS = 256;
 constexpr int NXCD = 8;
 constexpr int EPI_ROWS = 128;     // rows of a tile drained per epilogue part (LDS transpose buffer = EPI_ROWS x 132 floats)
-
-struct KArgs {
-    const float* a;
-    const float* wt;
-    bcos_tapconv_geom g;
-    bcos_epilogue e;
-    int M;          // N*P*Q
-    int PQ;
-    int Ktot;       // taps*C
-    int cpt;        // 16-byte chunks per tap = C/4
-    int nchunks;    // Ktot/4
-    int nk;         // K steps
-    int tiles_n;            // column tiles
-    int n_big, n_small;     // tiles of BM rows, then tiles of BM/2 rows (tail of the launch)
-    int rows_big;           // rows covered by the BM-row tiles
-    const void* wt3;              // optional pre-split weights in MFMA fragment order (bcos_split_weights), else NULL
-    unsigned wt3_bytes;
-    unsigned a_bytes, wt_bytes;   // operand sizes for the buffer descriptors of the split-bf16 path (< 2 GiB there)
-    const unsigned* a_absmax;     // split-f16 path: per-pixel max |A| bit patterns (the operand scale source)
-    unsigned absmax_bytes;
-    const unsigned* a_imgmax;     // ... per-image maxima of those (input-patch loop, tile_body_p), else NULL
-    const unsigned* a_imgmin;     // ... per-image minima over the NONZERO pixels of those (dynamic range inside an image), else NULL
-    const unsigned* a_imgmin_c;   // ... or a LOWER BOUND of those minima, stored complemented (~v; 0 = no nonzero pixel), as the epilogue of the launch that
-                                  //     produced A leaves it (bcos_epilogue.out_imgmin_c): decides only whether a tile runs the level bookkeeping, never a bit
-    int lvl_on;                   // input-patch loop: 1 = one pass per operand-scale level present in a tile (BCOS_OPT_PATCH_LEVELS)
-    int lvl_off;                  // input-patch loop: byte offset, inside the dynamic LDS, of the row-level table (beyond everything the epilogue uses)
-    const void* wt2;              // split-f16 path: pre-split, pre-scaled weights in MFMA fragment order (bcos_split_weights_f16x2)
-    unsigned wt2_bytes;
-    const float* wt2_cinv;        // ... their inverse column scales [padded Cout]
-    int h2;          // contraction on split-f16 MFMA (see tile_body_h2)
-    int x3;          // contraction on split-bf16 MFMA (see tile_body_x3) instead of fp32 MFMA
-    int uniform_tap; // C % 32 == 0: every K-step lies inside one tap
-    int vec_ok;     // every per-element epilogue tensor is 16-byte addressable (pitch % 4 == 0, aligned bases)
-    int epi_kind;   // 0 = general epilogue, k + 1 = specialisation k of EPI_KINDS_FWD (norm launches) / EPI_KINDS_BWD (tile_epilogue_fast)
-    unsigned out_bytes;   // size of the [N*OH*OW][out_pitch] epilogue tensors (epi_kind > 0: < 2 GiB)
-    // 2-D row tiles (input-patch loop on wide images, tile_body_p<..., T2D>): tile t = (image t / t2_nb, block t % t2_nb) and row r of a
-    // tile is position (r / t2_bw, r % t2_bw) of that t2_bh x t2_bw block of the row grid; 0 = rows are m = n P Q + i Q + j
-    int t2_bw, t2_nbx, t2_nb, t2_rows;
-};
 
 // row r of the tile at m0 -> (image, grid position), false: the tile has no such row (shared by the epilogues)
 template <typename P>
@@ -556,15 +511,7 @@ __device__ __forceinline__ void epi_part_generic(float* smem, const int pm, cons
 //     loads, so the loop body has no predicates,
 //   * keeps the per-row values (output offset, 1 / norm, inverse operand scale, pixel index) as one 16-byte LDS record.
 // Anything else (MaxOut, B != 2, GELU, replayed gates, ragged Cout, tensors >= 2 GiB, ...) takes the general epilogue.
-enum : int { EF_ADDEND = 1, EF_RELU = 2, EF_SCALE_OUT = 4, EF_MUL = 8, EF_OUT2 = 16, EF_MUL2 = 32, EF_GELU = 64, EF_MULACT = 128, EF_ROWADD = 256, EF_NONE = -1 };
-// forward kinds (NORM kernels): B = 2 scale, optional bias / channel affine;  backward kinds (no norm): gradient multipliers
-// (the GELU kinds are the linear1 layers of the B-cosified ViTs: MyGELU with its gate folded into the stored multiplier)
-constexpr int EPI_KINDS_FWD[] = {EF_RELU | EF_SCALE_OUT, EF_RELU | EF_SCALE_OUT | EF_ADDEND, EF_SCALE_OUT, EF_RELU, EF_RELU | EF_ADDEND, 0,
-                                 EF_GELU | EF_SCALE_OUT, EF_GELU};
-constexpr int EPI_KINDS_BWD[] = {EF_MUL, EF_MUL | EF_ADDEND | EF_OUT2, EF_MUL | EF_ADDEND | EF_OUT2 | EF_MUL2, 0, EF_ADDEND, EF_MUL | EF_OUT2,
-                                 EF_MUL | EF_MULACT, EF_ADDEND | EF_ROWADD};       // MULACT: the multiplier is rebuilt from the kept activation (BCOS_EPI_MUL_FROM_ACT);
-                                                                                   // ROWADD: out = acc + (rowadd_scale[pixel] rowadd + addend), the addend optional (bcos_epilogue.rowadd)
-constexpr int N_EPI_KINDS = 8;
+// (The EF_* bits and the kinds EPI_KINDS_FWD / EPI_KINDS_BWD: bcos_tapconv_plan.h, the dispatcher selects among them.)
 
 struct __attribute__((aligned(16))) EpiRow { unsigned off; float rinv; float ainv; int pix; };
 
@@ -1157,7 +1104,7 @@ __device__ __forceinline__ void tile_body(const KArgs& p, float* smem, const int
 // step through two LDS buffers: while the 6*TM*TN MFMAs of step k run, step k+1 is converted and written to the
 // other buffer and the global loads of step k+2 are in flight (one barrier per step).
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-constexpr int X3_BK = 16;      // k per step = one MFMA k-block; two LDS buffers
+// (X3_BK = 16, the k per step = one MFMA k-block through two LDS buffers: bcos_tapconv_plan.h)
 constexpr int X3_ROW = 32;     // bytes per LDS row of one split: 16 bf16, unpadded; the two 16-B halves of a row are swapped
                                // when bit 3 of the row index is set, which makes both the 8-byte staging stores (4 rows x 32 B
                                // per 16-lane group) and the 16-byte fragment reads (16 rows per group) bank-conflict free
@@ -1447,7 +1394,7 @@ constexpr int LVL_STEP = 16;       // operand-scale ladder of the per-image scal
                                    // there: every element of the row is off by <= 2^-23 of the row's maximum, ~1e-7 of ||patch|| ||w|| in the contraction
                                    // (measured: tests/test_gpu_parity.py::test_patch_loop_dynamic_range_inside_an_image); 12 costs 1.1 % of the ResNet-50
                                    // step on smooth synthetic images (level contours cross many tiles of the 56^2 / 112^2 gradient launches), 16 nothing
-constexpr int H2_MAX_TAPS = 16;    // channel-chunk-major K walk for up to this many taps (offset table: taps x BM x 4 bytes of LDS)
+// (H2_MAX_TAPS, the most taps the channel-chunk-major K walk takes: bcos_tapconv_plan.h)
 #ifndef H2_KO
 #define H2_KO 0                   // development knock-outs (timing only, wrong results): 1 no MFMA, 2 no split VALU, 4 no global loads in the loop, 8 no fragment reads
 #endif
@@ -3062,7 +3009,6 @@ __global__ __launch_bounds__(NTHREADS, (BN <= 32 && P_WGS3) ? 3 : 2) void tappat
 //  accumulator registers, four waves per SIMD -- was measured on the ResNet-50 shapes: 186 vs 211 TFLOP/s at M = 50 176,
 //  K = 2304 and within +-3 % elsewhere.  More waves per SIMD do not lift the loop; tile_body_h2 keeps its thread-count
 //  parameter, the kernel variant was dropped.)
-constexpr int SLOTS = 512;   // 256 CUs x 2 resident workgroups (LDS- and VGPR-limited)
 
 // tile counts of a launch: n_big tiles of BM rows, then n_small half-height tiles (see tapconv_kernel)
 template <int BM, int BN, int WAVES_M>
@@ -3098,16 +3044,7 @@ constexpr size_t epilogue_lds() {
     return (size_t)SBM * (SBN + 4) * sizeof(float) + (size_t)BM * 20 + (size_t)BN * 4 + (size_t)BM * 8 + 144;      // (+ the row maxima of the column parts + the per-image range cells)
 }
 
-// The launcher families (launch_cfg / launch_h2 / launch_d / launch_p) and the contraction loop a family's launch runs, numbered like BCOS_LOOP_* of
-// include/bcos_hip.h: the one place that decides it, for launch_cfg (the LOOP template argument of its kernel) and for bcos_tapconv_route_query
-enum : int { BCOS_FAM_CFG, BCOS_FAM_H2, BCOS_FAM_D, BCOS_FAM_P };
-inline int family_loop(int fam, const KArgs& p) {
-    if (fam == BCOS_FAM_CFG) return p.x3 ? (p.wt3 ? BCOS_LOOP_BF16X3_PRESPLIT : BCOS_LOOP_BF16X3) : BCOS_LOOP_F32;
-    return fam == BCOS_FAM_H2 ? BCOS_LOOP_F16X2_REGS : fam == BCOS_FAM_D ? BCOS_LOOP_F16X2_DMA : BCOS_LOOP_F16X2_PATCH;
-}
-static_assert(BCOS_LOOP_F32 == 0 && BCOS_LOOP_BF16X3 == 1 && BCOS_LOOP_BF16X3_PRESPLIT == 2, "family_loop returns the kernel's LOOP argument");
-
-// The launch of every family: raise the kernel's dynamic-LDS limit if this launch needs more than any before it (`lds_hw`: the high-water
+// The launch of every family (launch_cfg / launch_h2 / launch_d / launch_p; BCOS_FAM_* and family_loop: bcos_tapconv_plan.h): raise the kernel's dynamic-LDS limit if this launch needs more than any before it (`lds_hw`: the high-water
 // mark, a static of the caller per kernel instantiation), launch, and turn a HIP error into BCOS_E_LAUNCH
 template <class Kernel>
 int launch_tiles(Kernel k, dim3 grid, size_t lds, hipStream_t stream, const KArgs& p, std::atomic<size_t>& lds_hw) {
@@ -3214,20 +3151,6 @@ int launch_p(const KArgs& base, bool norm, hipStream_t stream) {
                 : launch_tiles(tappatch_kernel<BM, BN, WAVES_M, WAVES_N, false, NI, PXL, NTAPS, T2BW>, grid, lds, stream, p, lds_hw[1]);
 }
 
-// Does the input patch of every BM-row tile of the launch fit `px` pixels?  Upper bound over the tile positions: a tile touches
-// at most R = (BM + Q - 2) / Q + 1 output rows, which cross at most ceil((R - 1) / P) image boundaries (TH - s extra virtual rows each)
-inline bool patch_fits(const bcos_tapconv_geom& g, int BM, int items_px, int lds_px) {
-    const int s = g.in_sh;
-    const int R = (BM + g.Q - 2) / g.Q + 1;
-    const int nb = (R - 1 + g.P - 1) / g.P;
-    const int extra = g.TH > s ? g.TH - s : 0;
-    const int64_t rows = (int64_t)(R - 1) * s + g.TH + (int64_t)nb * extra;
-    const int pw = (g.Q - 1) * s + g.TW;
-    int pitch = 1;
-    while (pitch < pw) pitch <<= 1;                                  // (rows are stored with a power-of-two pitch, rotated: tile_body_p)
-    return rows * pw <= items_px && rows * pitch <= lds_px && (int64_t)g.P * g.Q * 14 >= BM;      // (at most 16 images per tile)
-}
-
 }  // namespace
 
 #if BCOS_PHASE_TIMING
@@ -3249,46 +3172,14 @@ extern "C" int BCOS_PH_NAME(BCOS_TAPCONV_PART)(unsigned long long* out) {
 #endif
 #endif
 
-// The file is compiled either whole or in slices (-DBCOS_TAPCONV_PART=k, bcos_hip/lib.py: build): slice 0 carries the C ABI
-// and the small tile configurations, slices 1.. the kernel instantiations of one or two tile configurations each.  The
-// launchers cross slices as plain functions taking the launch descriptor by address (every slice compiles the same KArgs).
+// The file is compiled either whole or in slices (-DBCOS_TAPCONV_PART=k, bcos_hip/lib.py: build): every slice carries the kernel
+// instantiations of one to three tile configurations and nothing else.  The launchers cross slices, and reach the dispatcher
+// (bcos_tapconv_dispatch.hip), as plain functions taking the launch descriptor by address (every unit compiles the same KArgs):
+// BCOS_TC_LAUNCHER and the list BCOS_TC_ROUTES, bcos_tapconv_plan.h.
 #ifndef BCOS_TAPCONV_PART
 #define BCOS_TAPCONV_PART -1
 #endif
 #define BCOS_TC_IN(k) (BCOS_TAPCONV_PART == -1 || BCOS_TAPCONV_PART == (k))
-#define BCOS_TC_LAUNCHER(name) __attribute__((visibility("hidden"))) int name(const void* kargs, int norm, hipStream_t s)
-// every tile launcher, once: X(name, launcher family (BCOS_FAM_*: which loop it instantiates, family_loop), tile rows, tile columns).  The list declares the launchers, numbers them (the route ids of
-// bcos_tapconv_route_query, the narrow-output kernel of bcos_skinny.hip last) and fills the table the dispatcher launches through;
-// BCOS_TC_DEFINE refuses a launcher that is not in it, and one that is listed without a definition does not link
-#define BCOS_TC_ROUTES(X) \
-    X(cfg_128x128, BCOS_FAM_CFG, 128, 128) \
-    X(cfg_128x64, BCOS_FAM_CFG, 128, 64) \
-    X(cfg_128x32, BCOS_FAM_CFG, 128, 32) \
-    X(h2_128x256, BCOS_FAM_H2, 128, 256) \
-    X(h2_128x128, BCOS_FAM_H2, 128, 128) \
-    X(h2_128x64, BCOS_FAM_H2, 128, 64) \
-    X(h2_128x32, BCOS_FAM_H2, 128, 32) \
-    X(h2_256x64, BCOS_FAM_H2, 256, 64) \
-    X(h2_256x32, BCOS_FAM_H2, 256, 32) \
-    X(d_128x256, BCOS_FAM_D, 128, 256) \
-    X(d_128x128, BCOS_FAM_D, 128, 128) \
-    X(d_128x192, BCOS_FAM_D, 128, 192) \
-    X(d_128x64, BCOS_FAM_D, 128, 64) \
-    X(d_128x32, BCOS_FAM_D, 128, 32) \
-    X(d_256x64, BCOS_FAM_D, 256, 64) \
-    X(d_256x32, BCOS_FAM_D, 256, 32) \
-    X(p_128x256_a, BCOS_FAM_P, 128, 256) \
-    X(p_128x128_a, BCOS_FAM_P, 128, 128) \
-    X(p_128x128_b, BCOS_FAM_P, 128, 128) \
-    X(p_128x128_c, BCOS_FAM_P, 128, 128) \
-    X(p_256x64_a, BCOS_FAM_P, 256, 64) \
-    X(p2_256x32_t16, BCOS_FAM_P, 256, 32) \
-    X(p2_256x32_t9, BCOS_FAM_P, 256, 32) \
-    X(p2_256x64_b32, BCOS_FAM_P, 256, 64)
-#define BCOS_TC_X_DECL(name, fam, bm, bn) BCOS_TC_LAUNCHER(bcos_tc_##name);
-BCOS_TC_ROUTES(BCOS_TC_X_DECL)
-#define BCOS_TC_X_ID(name, fam, bm, bn) ROUTE_##name,
-enum : int { BCOS_TC_ROUTES(BCOS_TC_X_ID) ROUTE_skinny, ROUTE_COUNT };
 #define BCOS_TC_DEFINE(name, call) static_assert(ROUTE_##name >= 0, "launcher missing from BCOS_TC_ROUTES"); BCOS_TC_LAUNCHER(bcos_tc_##name) { return call(*static_cast<const KArgs*>(kargs), norm != 0, s); }
 #if BCOS_TC_IN(1)
 BCOS_TC_DEFINE(cfg_128x128, (launch_cfg<128, 128, 2, 2>))
@@ -3340,893 +3231,4 @@ BCOS_TC_DEFINE(p_128x128_c, (launch_p<128, 128, 2, 2, 3, 320, 9>))      // 28^2:
 #if BCOS_TC_IN(0)
 BCOS_TC_DEFINE(h2_128x64, (launch_h2<128, 64, 2, 2>))
 BCOS_TC_DEFINE(h2_128x32, (launch_h2<128, 32, 4, 1>))
-
-extern "C" int bcos_set_contraction_mode(int mode) {
-    if (mode < 0 || mode > 2)
-        return bcos_set_error(BCOS_E_INVAL, "bcos_set_contraction_mode: 0 = fp32 MFMA, 1 = split-bf16 MFMA, 2 = split-f16 MFMA");
-    g_contraction_mode = mode;
-    return BCOS_OK;
-}
-
-extern "C" int bcos_get_contraction_mode(void) { return g_contraction_mode; }
-
-
-namespace {
-
-// wt [rows][Ktot] fp32 -> wt3 [32-row tile][16-k step][plane h|m|l][lane][8 bf16]: lane = (row % 32) + 32 * ((k % 16) / 8),
-// i.e. the B operand of v_mfma_f32_32x32x16_bf16 for that (tile, step); rows are padded to a multiple of 128 and k to a
-// multiple of 16 with zeros.  Same truncating split as tile_body_x3::split_store (bit-identical products).
-__global__ __launch_bounds__(256) void split_weights_kernel(const float* __restrict__ wt, uint4* __restrict__ wt3, int rows,
-                                                            int Ktot, int nk, int64_t total) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;        // (tile, ks, lane)
-    if (i >= total) return;
-    const int lane = (int)(i & 63);
-    const int64_t ts = i >> 6;
-    const int ks = (int)(ts % nk);
-    const int tile = (int)(ts / nk);
-    const int row = tile * 32 + (lane & 31);
-    const int k0 = ks * 16 + 8 * (lane >> 5);
-    unsigned h[8], m[8], l[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const float x = (row < rows && k0 + e < Ktot) ? wt[(int64_t)row * Ktot + k0 + e] : 0.f;
-        h[e] = __float_as_uint(x) & 0xffff0000u;
-        const float r1 = x - __uint_as_float(h[e]);
-        m[e] = __float_as_uint(r1) & 0xffff0000u;
-        l[e] = __float_as_uint(r1 - __uint_as_float(m[e])) & 0xffff0000u;
-    }
-    auto pack = [](const unsigned (&v)[8]) {
-        return uint4{(v[0] >> 16) | v[1], (v[2] >> 16) | v[3], (v[4] >> 16) | v[5], (v[6] >> 16) | v[7]};
-    };
-    uint4* dst = wt3 + (ts * 3) * 64 + lane;
-    dst[0] = pack(h);
-    dst[64] = pack(m);
-    dst[128] = pack(l);
-}
-
-inline int64_t split_bytes(int rows, int Ktot) {
-    const int64_t tiles = (((int64_t)rows + 127) / 128) * 4, nk = ((int64_t)Ktot + 15) / 16;
-    return tiles * nk * 3 * 1024;
-}
-
-}  // namespace
-
-extern "C" int bcos_split_weights_bytes(int rows, int Ktot, int64_t* bytes) {
-    if (rows <= 0 || Ktot <= 0 || !bytes) return bcos_set_error(BCOS_E_INVAL, "bcos_split_weights_bytes: bad argument");
-    *bytes = split_bytes(rows, Ktot);
-    return BCOS_OK;
-}
-
-extern "C" int bcos_split_weights(const float* wt, void* wt3, int rows, int Ktot, void* stream) {
-    if (!wt || !wt3 || rows <= 0 || Ktot <= 0) return bcos_set_error(BCOS_E_INVAL, "bcos_split_weights: bad argument");
-    if (reinterpret_cast<uintptr_t>(wt3) & 15) return bcos_set_error(BCOS_E_INVAL, "bcos_split_weights: wt3 must be 16-byte aligned");
-    const int nk = (Ktot + 15) / 16;
-    const int64_t total = split_bytes(rows, Ktot) / (3 * 16);
-    hipLaunchKernelGGL(split_weights_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
-                       reinterpret_cast<hipStream_t>(stream), wt, reinterpret_cast<uint4*>(wt3), rows, Ktot, nk, total);
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return bcos_set_hip_error("split_weights launch", err);
-    return BCOS_OK;
-}
-
-namespace {
-
-// f16x2 image of wt [rows][Ktot]: [32-row tile][16-k step][plane h|l][lane][8 f16] (B fragments of v_mfma_f32_32x32x16_f16,
-// rows padded to a multiple of 128, k to a multiple of 16) followed by the inverse row scales float[padded rows].
-// Row r is scaled by 2^e_r so that its max |w| lands in [2^14, 2^15) before the split (exact), cinv[r] = 2^-e_r.
-__global__ __launch_bounds__(256) void weight_rowscale_kernel(const float* __restrict__ wt, float* __restrict__ cinv, int rows,
-                                                              int rows_pad, int Ktot) {
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (row >= rows_pad) return;
-    unsigned m = 0u;
-    if (row < rows)
-        for (int k = lane; k < Ktot; k += 64) m = max(m, absbits(wt[(int64_t)row * Ktot + k]));
-    m = wave_max_u32(m);
-    if (lane == 0) cinv[row] = f16x2_inv(f16x2_exp(m));
-}
-
-__global__ __launch_bounds__(256) void split_weights_h2_kernel(const float* __restrict__ wt, uint4* __restrict__ wt2,
-                                                               const float* __restrict__ cinv, int rows, int Ktot, int nk,
-                                                               int64_t total, int taps, int C) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;        // (tile, ks, lane)
-    if (i >= total) return;
-    const int lane = (int)(i & 63);
-    const int64_t ts = i >> 6;
-    const int ks = (int)(ts % nk);
-    const int tile = (int)(ts / nk);
-    const int row = tile * 32 + (lane & 31);
-    // k of the 8 elements: plain order, or (taps > 1) channel-chunk-major: step ks = tap ks % taps of 16-channel chunk ks / taps
-    const int k0 = taps > 1 ? (ks % taps) * C + (ks / taps) * 16 + 8 * (lane >> 5) : ks * 16 + 8 * (lane >> 5);
-    const float scale = 1.0f / cinv[row];                             // exact: a power of two
-    f16x8 h, l;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const float x = (row < rows && k0 + e < Ktot) ? wt[(int64_t)row * Ktot + k0 + e] * scale : 0.f;
-        const _Float16 hh = (_Float16)x;
-        h[e] = hh;
-        l[e] = (_Float16)(x - (float)hh);
-    }
-    uint4* dst = wt2 + (ts * 2) * 64 + lane;
-    dst[0] = __builtin_bit_cast(uint4, h);
-    dst[64] = __builtin_bit_cast(uint4, l);
-}
-
-// both steps in one launch for small weight tensors (one workgroup per 32-row tile: row maxima, then its fragments) -- a training step
-// re-splits every weight twice (the forward and the transposed input-gradient image), ~100 images of 37-400 K elements for ViT-Ti:
-// half the launches of that for the block weights.  Same arithmetic as the two kernels above.
-__global__ __launch_bounds__(256) void split_weights_h2_fused_kernel(const float* __restrict__ wt, uint4* __restrict__ wt2,
-                                                                     float* __restrict__ cinv, int rows, int Ktot, int nk, int taps, int C) {
-    // grid (32-row tile, K part): every workgroup takes the maxima of its tile's rows (coalesced 16-byte loads, the rows meet in LDS
-    // atomics; redundant across the K parts: the tensors are L2-sized) and writes the fragments of its share of the 16-k steps
-    __shared__ unsigned s_max[32];
-    __shared__ float s_scale[32];
-    const int tile = blockIdx.x, tid = threadIdx.x;
-    if (tid < 32) s_max[tid] = 0u;
-    __syncthreads();
-    const int row0 = tile * 32;
-    const int live = rows - row0 < 32 ? rows - row0 : 32;
-    const float* base = wt + (int64_t)row0 * Ktot;
-    if ((Ktot & 3) == 0 && !(reinterpret_cast<uintptr_t>(wt) & 15)) {
-        const int per_row = Ktot >> 2, n4 = live * per_row;
-        for (int i = tid; i < n4; i += 256) {
-            const f32x4 v = reinterpret_cast<const f32x4*>(base)[i];
-            unsigned m = 0u;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) m = max(m, __float_as_uint(v[q]) & 0x7fffffffu);
-            atomicMax(&s_max[i / per_row], m);
-        }
-    } else {
-        const int n = live * Ktot;
-        for (int i = tid; i < n; i += 256) atomicMax(&s_max[i / Ktot], __float_as_uint(base[i]) & 0x7fffffffu);
-    }
-    __syncthreads();
-    if (tid < 32) {
-        const float ci = f16x2_inv(f16x2_exp(s_max[tid]));
-        if (blockIdx.y == 0) cinv[row0 + tid] = ci;
-        s_scale[tid] = 1.0f / ci;                                     // exact: a power of two
-    }
-    __syncthreads();
-    const int lane = tid & 63;
-    const int row = row0 + (lane & 31);
-    const float scale = s_scale[lane & 31];
-    for (int ks = (int)blockIdx.y * 4 + (tid >> 6); ks < nk; ks += 4 * (int)gridDim.y) {
-        const int k0 = taps > 1 ? (ks % taps) * C + (ks / taps) * 16 + 8 * (lane >> 5) : ks * 16 + 8 * (lane >> 5);
-        f16x8 h, l;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const float x = (row < rows && k0 + e < Ktot) ? wt[(int64_t)row * Ktot + k0 + e] * scale : 0.f;
-            const _Float16 hh = (_Float16)x;
-            h[e] = hh;
-            l[e] = (_Float16)(x - (float)hh);
-        }
-        uint4* dst = wt2 + ((int64_t)tile * nk + ks) * 2 * 64 + lane;
-        dst[0] = __builtin_bit_cast(uint4, h);
-        dst[64] = __builtin_bit_cast(uint4, l);
-    }
-}
-
-__host__ __device__ inline int64_t h2_tiles(int rows) { return (((int64_t)rows + 127) / 128) * 4; }
-__host__ __device__ inline int64_t h2_image_bytes(int rows, int Ktot) { return h2_tiles(rows) * (((int64_t)Ktot + 15) / 16) * 2 * 1024; }
-
-}  // namespace
-
-extern "C" int bcos_split_weights_f16x2_bytes(int rows, int Ktot, int64_t* bytes) {
-    if (rows <= 0 || Ktot <= 0 || !bytes) return bcos_set_error(BCOS_E_INVAL, "bcos_split_weights_f16x2_bytes: bad argument");
-    *bytes = h2_image_bytes(rows, Ktot) + h2_tiles(rows) * 32 * 4;
-    return BCOS_OK;
-}
-
-extern "C" int bcos_split_weights_f16x2(const float* wt, void* wt2, int rows, int Ktot, void* stream) {
-    return bcos_split_weights_f16x2_conv(wt, wt2, rows, 1, Ktot, stream);
-}
-
-extern "C" int bcos_split_weights_f16x2_conv(const float* wt, void* wt2, int rows, int taps, int C, void* stream) {
-    if (taps <= 0 || C <= 0) return bcos_set_error(BCOS_E_INVAL, "bcos_split_weights_f16x2: bad argument");
-    const int Ktot = taps * C;
-    // the kernel walks K channel-chunk-major exactly when this holds (tile_body_h2: kmajor)
-    const int ktaps = (taps > 1 && taps <= H2_MAX_TAPS && C % 16 == 0) ? taps : 1;
-    if (!wt || !wt2 || rows <= 0 || Ktot <= 0) return bcos_set_error(BCOS_E_INVAL, "bcos_split_weights_f16x2: bad argument");
-    if (reinterpret_cast<uintptr_t>(wt2) & 15) return bcos_set_error(BCOS_E_INVAL, "bcos_split_weights_f16x2: image must be 16-byte aligned");
-    const int nk = (Ktot + 15) / 16;
-    const int rows_pad = (int)h2_tiles(rows) * 32;
-    float* cinv = reinterpret_cast<float*>(static_cast<char*>(wt2) + h2_image_bytes(rows, Ktot));
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    // (one workgroup per 32 rows walks its whole K: beyond ~150 K elements or K > 1024 the two wide launches are faster -- at 2^20
-    //  elements the one-launch form cost a ResNet-50 training step 43 us per image, 4.6 ms per step)
-    if ((int64_t)rows_pad * Ktot <= 160 * 1024 && Ktot <= 1024) {
-        int parts = nk / 8;                                   // two 16-k steps per wave and workgroup
-        parts = parts < 1 ? 1 : (parts > 8 ? 8 : parts);
-        hipLaunchKernelGGL(split_weights_h2_fused_kernel, dim3((unsigned)h2_tiles(rows), (unsigned)parts), dim3(256), 0, s, wt,
-                           reinterpret_cast<uint4*>(wt2), cinv, rows, Ktot, nk, ktaps, C);
-    } else {
-        hipLaunchKernelGGL(weight_rowscale_kernel, dim3((unsigned)((rows_pad + 3) / 4)), dim3(256), 0, s, wt, cinv, rows, rows_pad, Ktot);
-        const int64_t total = h2_tiles(rows) * nk * 64;
-        hipLaunchKernelGGL(split_weights_h2_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, wt,
-                           reinterpret_cast<uint4*>(wt2), cinv, rows, Ktot, nk, total, ktaps, C);
-    }
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return bcos_set_hip_error("split_weights_f16x2 launch", err);
-    return BCOS_OK;
-}
-
-// ---- banks + images of many layers from one call (bcos_weight_prep_batch) ---------------------------------------------------------------
-namespace {
-constexpr int PREP_KCH = 1024;          // bank elements of a row per workgroup of the gather
-// (1) grid (32-row tile x K part, jobs): gather the part's elements of the tile's rows from the strided source into the bank (coalesced
-//     along K) and fold their maxima into row_max[job.row_offset + row] (zero-filled by the caller): per thread, per wave, then ONE atomic per
-//     row and workgroup.
-__global__ __launch_bounds__(256) void weight_prep_gather_kernel(const bcos_weight_prep_job* __restrict__ jobs, unsigned* __restrict__ row_max) {
-    const bcos_weight_prep_job& jb = jobs[blockIdx.y];
-    const int rows = jb.rows, Cp = jb.Cp, channels = jb.channels;
-    const int Ktot = jb.taps * Cp;
-    const int kparts = (Ktot + PREP_KCH - 1) / PREP_KCH;
-    const int tile = (int)blockIdx.x / kparts, kpart = (int)blockIdx.x - tile * kparts;
-    const int row0 = tile * 32;
-    if (row0 >= rows) return;
-    const int live = rows - row0 < 32 ? rows - row0 : 32;
-    const int k_lo = kpart * PREP_KCH, k_hi = k_lo + PREP_KCH < Ktot ? k_lo + PREP_KCH : Ktot;
-    const float* __restrict__ src = jb.src;
-    float* __restrict__ bank = jb.bank;
-    const int tid = threadIdx.x;
-    // (t, c) of this thread's elements do not depend on the row: decoded once
-    int off[PREP_KCH / 256];
-    bool in[PREP_KCH / 256];
-#pragma unroll
-    for (int q = 0; q < PREP_KCH / 256; ++q) {
-        const int k = k_lo + q * 256 + tid;
-        const int t = k / Cp, c = k - t * Cp;
-        in[q] = k < k_hi && c < channels && t < jb.taps;
-        off[q] = in[q] ? c * jb.ch_stride + jb.tap_offset[t] : 0;
-    }
-    // rows in groups of eight: eight independent loads in flight per thread and K part, then the stores and the rows' maxima
-#pragma unroll
-    for (int q = 0; q < PREP_KCH / 256; ++q) {
-        const int k = k_lo + q * 256 + tid;
-        if (k_lo + q * 256 >= k_hi) break;
-        for (int r0 = 0; r0 < live; r0 += 8) {
-            float v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u)
-                v[u] = (in[q] && r0 + u < live) ? src[(int64_t)(row0 + r0 + u) * jb.row_stride + off[q]] : 0.f;
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                if (r0 + u < live) {            // (uniform over the workgroup)
-                    if (k < k_hi) bank[(int64_t)(row0 + r0 + u) * Ktot + k] = v[u];
-                    const unsigned m = wave_max_u32(k < k_hi ? absbits(v[u]) : 0u);
-                    if ((tid & 63) == 0 && m) atomicMax(row_max + jb.row_offset + row0 + r0 + u, m);
-                }
-            }
-        }
-    }
-}
-
-// (2) grid (32-row tile x group of 16-k steps, jobs): the image of the bank -- the arithmetic of weight_rowscale_kernel + split_weights_h2_kernel
-//     on the bank's values and the rows' maxima: that pair's image bit for bit.
-__global__ __launch_bounds__(256) void weight_prep_split_kernel(const bcos_weight_prep_job* __restrict__ jobs, const unsigned* __restrict__ row_max) {
-    const bcos_weight_prep_job& jb = jobs[blockIdx.y];
-    if (jb.image == nullptr) return;
-    const int rows = jb.rows, taps = jb.taps, Cp = jb.Cp;
-    const int Ktot = taps * Cp;
-    const int nk = (Ktot + 15) / 16;
-    constexpr int KS_PER_WG = PREP_KCH / 16;                    // 64 steps (16 per wave)
-    const int kgroups = (nk + KS_PER_WG - 1) / KS_PER_WG;
-    const int tiles = (int)h2_tiles(rows);                       // (the image is padded to a multiple of 128 rows: empty tiles hold zeros)
-    const int tile = (int)blockIdx.x / kgroups, kgroup = (int)blockIdx.x - tile * kgroups;
-    if (tile >= tiles) return;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int row = tile * 32 + (lane & 31);
-    const float ci = f16x2_inv(f16x2_exp(row < rows ? row_max[jb.row_offset + row] : 0u));
-    const float scale = 1.0f / ci;                                // exact: a power of two
-    uint4* wt2 = reinterpret_cast<uint4*>(jb.image);
-    if (kgroup == 0 && tid < 32) reinterpret_cast<float*>(static_cast<char*>(jb.image) + h2_image_bytes(rows, Ktot))[tile * 32 + tid] = ci;
-    const float* __restrict__ bank = jb.bank;
-    const int ktaps = (taps > 1 && taps <= H2_MAX_TAPS && Cp % 16 == 0) ? taps : 1;      // (bcos_split_weights_f16x2_conv: channel-chunk-major K)
-    const int ks_hi = (kgroup + 1) * KS_PER_WG < nk ? (kgroup + 1) * KS_PER_WG : nk;
-    for (int ks = kgroup * KS_PER_WG + (tid >> 6); ks < ks_hi; ks += 4) {
-        const int k0 = ktaps > 1 ? (ks % ktaps) * Cp + (ks / ktaps) * 16 + 8 * (lane >> 5) : ks * 16 + 8 * (lane >> 5);
-        f16x8 h, l;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const float x = (row < rows && k0 + e < Ktot) ? bank[(int64_t)row * Ktot + k0 + e] * scale : 0.f;
-            const _Float16 hh = (_Float16)x;
-            h[e] = hh;
-            l[e] = (_Float16)(x - (float)hh);
-        }
-        uint4* dst = wt2 + ((int64_t)tile * nk + ks) * 2 * 64 + lane;
-        dst[0] = __builtin_bit_cast(uint4, h);
-        dst[64] = __builtin_bit_cast(uint4, l);
-    }
-}
-}  // namespace
-
-extern "C" int bcos_weight_prep_batch(const bcos_weight_prep_job* jobs, int njobs, int max_rows, int max_ktot, uint32_t* row_max, void* stream) {
-    if (!jobs || !row_max || njobs <= 0 || njobs > 65535 || max_rows <= 0 || max_ktot <= 0)
-        return bcos_set_error(BCOS_E_INVAL, "bcos_weight_prep_batch: bad argument");
-    if (reinterpret_cast<uintptr_t>(jobs) & 7) return bcos_set_error(BCOS_E_INVAL, "bcos_weight_prep_batch: job table must be 8-byte aligned");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const int64_t tiles = h2_tiles(max_rows);
-    const int64_t kparts = ((int64_t)max_ktot + PREP_KCH - 1) / PREP_KCH;
-    if (tiles * kparts > 0x7fffffff) return bcos_set_error(BCOS_E_NOSUP, "bcos_weight_prep_batch: too large");
-    hipLaunchKernelGGL(weight_prep_gather_kernel, dim3((unsigned)(tiles * kparts), (unsigned)njobs), dim3(256), 0, s, jobs, row_max);
-    hipLaunchKernelGGL(weight_prep_split_kernel, dim3((unsigned)(tiles * kparts), (unsigned)njobs), dim3(256), 0, s, jobs, row_max);
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return bcos_set_hip_error("weight_prep_batch launch", err);
-    return BCOS_OK;
-}
-
-// per-pixel max |x| bit patterns of an NHWC tensor (for tensors whose producer is not a tapconv epilogue)
-namespace {
-__global__ __launch_bounds__(256) void rows_absmax_kernel(const float* __restrict__ x, unsigned* __restrict__ out, int64_t rows,
-                                                          int C, int pitch) {
-    // LPR lanes per row (power of two <= 64), float4 loads
-    int lpr = 1;
-    while (lpr < 64 && lpr * 4 < C) lpr <<= 1;
-    const int rpw = 64 / lpr;
-    const int lane = threadIdx.x & 63;
-    const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int64_t row = wave * rpw + lane / lpr;
-    const int sub = lane % lpr;
-    unsigned m = 0u;
-    if (row < rows) {
-        const float* src = x + row * pitch;
-        for (int c = sub * 4; c < C; c += lpr * 4) {
-            const f32x4 v = *reinterpret_cast<const f32x4*>(src + c);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) m = max(m, __float_as_uint(v[q]) & 0x7fffffffu);
-        }
-    }
-    for (int o = lpr >> 1; o >= 1; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o));
-    if (row < rows && sub == 0) out[row] = m;
-}
-}  // namespace
-
-namespace {
-__global__ __launch_bounds__(1024) void image_absmax_kernel(const unsigned* __restrict__ absmax, unsigned* __restrict__ out,
-                                                            unsigned* __restrict__ out_min, int hw) {
-    // one workgroup of 16 waves per image, four independent loads in flight per thread: the kernel is one load latency long.
-    // out_min (optional): the smallest NONZERO per-pixel maximum of the image (0xffffffff: every pixel is zero) -- with the
-    // image maximum, the dynamic range of the pixels inside the image (bcos_operands.a_imgmin)
-    __shared__ unsigned s_max[16], s_min[16];
-    const unsigned* src = absmax + (size_t)blockIdx.x * hw;
-    unsigned v = 0u, w = 0xffffffffu;
-    for (int i0 = 0; i0 < hw; i0 += 4096) {
-        unsigned u[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int i = i0 + q * 1024 + (int)threadIdx.x;
-            u[q] = i < hw ? src[i] : 0u;
-        }
-        v = max(max(v, u[0]), max(max(u[1], u[2]), u[3]));
-#pragma unroll
-        for (int q = 0; q < 4; ++q) w = min(w, u[q] - 1u);      // (0 - 1 wraps to the top: zero pixels never win)
-    }
-#pragma unroll
-    for (int o = 32; o; o >>= 1) {
-        v = max(v, (unsigned)__shfl_xor((int)v, o));
-        w = min(w, (unsigned)__shfl_xor((int)w, o));
-    }
-    if ((threadIdx.x & 63) == 0) { s_max[threadIdx.x >> 6] = v; s_min[threadIdx.x >> 6] = w; }
-    __syncthreads();
-    if (threadIdx.x < 16) {
-        unsigned m = s_max[threadIdx.x], mn = s_min[threadIdx.x];
-#pragma unroll
-        for (int o = 8; o; o >>= 1) {
-            m = max(m, (unsigned)__shfl_xor((int)m, o));
-            mn = min(mn, (unsigned)__shfl_xor((int)mn, o));
-        }
-        if (threadIdx.x == 0) {
-            out[blockIdx.x] = m;
-            if (out_min) out_min[blockIdx.x] = mn == 0xffffffffu ? mn : mn + 1u;
-        }
-    }
-}
-}  // namespace
-
-namespace {
-// the same range from SEVERAL workgroups per image (grid: image x part), for images of many pixels or a device that is busy with
-// another stream's launch: the parts meet by atomicMax in ZERO-FILLED words -- the minimum over the nonzero pixels as its complement
-// (~v; 0 = no nonzero pixel), the form the producing epilogues leave (bcos_epilogue.out_imgmin_c)
-__global__ __launch_bounds__(256) void image_absrange_c_kernel(const unsigned* __restrict__ absmax, unsigned* __restrict__ out_max,
-                                                               unsigned* __restrict__ out_min_c, int hw, int per_part) {
-    __shared__ unsigned s_max[4], s_min[4];
-    const unsigned* src = absmax + (size_t)blockIdx.x * hw;
-    const int lo = (int)blockIdx.y * per_part, hi = lo + per_part < hw ? lo + per_part : hw;
-    unsigned v = 0u, w = 0xffffffffu;
-    for (int i0 = lo; i0 < hi; i0 += 1024) {
-        unsigned u[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int i = i0 + q * 256 + (int)threadIdx.x;
-            u[q] = i < hi ? src[i] : 0u;
-        }
-        v = max(max(v, u[0]), max(max(u[1], u[2]), u[3]));
-#pragma unroll
-        for (int q = 0; q < 4; ++q) w = min(w, u[q] - 1u);      // (0 - 1 wraps to the top: zero pixels never win)
-    }
-#pragma unroll
-    for (int o = 32; o; o >>= 1) {
-        v = max(v, (unsigned)__shfl_xor((int)v, o));
-        w = min(w, (unsigned)__shfl_xor((int)w, o));
-    }
-    if ((threadIdx.x & 63) == 0) { s_max[threadIdx.x >> 6] = v; s_min[threadIdx.x >> 6] = w; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const unsigned m = max(max(s_max[0], s_max[1]), max(s_max[2], s_max[3]));
-        const unsigned mn = min(min(s_min[0], s_min[1]), min(s_min[2], s_min[3]));
-        if (m) atomicMax(out_max + blockIdx.x, m);
-        if (mn != 0xffffffffu) atomicMax(out_min_c + blockIdx.x, ~(mn + 1u));
-    }
-}
-}  // namespace
-
-extern "C" int bcos_image_absrange_c(const uint32_t* absmax, uint32_t* out_max, uint32_t* out_min_c, int n_images, int pixels_per_image,
-                                     void* stream) {
-    if (!absmax || !out_max || !out_min_c || n_images <= 0 || pixels_per_image <= 0)
-        return bcos_set_error(BCOS_E_INVAL, "bcos_image_absrange_c: bad argument");
-    // parts of >= 2 048 pixels, as many as put ~1 024 workgroups on the device
-    int parts = (pixels_per_image + 2047) / 2048;
-    const int want = (1024 + n_images - 1) / n_images;
-    parts = parts < 1 ? 1 : (parts > want ? want : parts);
-    const int per_part = (((pixels_per_image + parts - 1) / parts) + 255) & ~255;
-    parts = (pixels_per_image + per_part - 1) / per_part;
-    hipLaunchKernelGGL(image_absrange_c_kernel, dim3((unsigned)n_images, (unsigned)parts), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
-                       absmax, out_max, out_min_c, pixels_per_image, per_part);
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return bcos_set_hip_error("image_absrange_c launch", err);
-    return BCOS_OK;
-}
-
-extern "C" int bcos_image_absmax(const uint32_t* absmax, uint32_t* out, int n_images, int pixels_per_image, void* stream) {
-    return bcos_image_absrange(absmax, out, nullptr, n_images, pixels_per_image, stream);
-}
-
-extern "C" int bcos_image_absrange(const uint32_t* absmax, uint32_t* out_max, uint32_t* out_min, int n_images, int pixels_per_image,
-                                   void* stream) {
-    uint32_t* out = out_max;
-    if (!absmax || !out || n_images <= 0 || pixels_per_image <= 0) return bcos_set_error(BCOS_E_INVAL, "bcos_image_absmax: bad argument");
-    hipLaunchKernelGGL(image_absmax_kernel, dim3((unsigned)n_images), dim3(1024), 0, reinterpret_cast<hipStream_t>(stream), absmax, out,
-                       out_min, pixels_per_image);
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return bcos_set_hip_error("image_absmax launch", err);
-    return BCOS_OK;
-}
-
-extern "C" int bcos_rows_absmax(const float* x, uint32_t* out, int64_t rows, int C, int pitch, void* stream) {
-    if (!x || !out || rows <= 0 || C <= 0 || C % 4 != 0) return bcos_set_error(BCOS_E_INVAL, "bcos_rows_absmax: bad argument");
-    if (pitch == 0) pitch = C;
-    if (pitch % 4 != 0 || pitch < C || (reinterpret_cast<uintptr_t>(x) & 15))
-        return bcos_set_error(BCOS_E_INVAL, "bcos_rows_absmax: rows must be 16-byte addressable");
-    int lpr = 1;
-    while (lpr < 64 && lpr * 4 < C) lpr <<= 1;
-    const int64_t rows_per_block = 4 * (64 / lpr);
-    hipLaunchKernelGGL(rows_absmax_kernel, dim3((unsigned)((rows + rows_per_block - 1) / rows_per_block)), dim3(256), 0,
-                       reinterpret_cast<hipStream_t>(stream), x, out, rows, C, pitch);
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return bcos_set_hip_error("rows_absmax launch", err);
-    return BCOS_OK;
-}
-
-extern "C" int bcos_tapconv(const float* a, const float* wt, const bcos_tapconv_geom* geom,
-                            const bcos_epilogue* epi, void* stream) {
-    bcos_operands o = {a, nullptr, wt, nullptr, nullptr, BCOS_CONTRACT_DEFAULT, nullptr, nullptr};
-    return bcos_tapconv_ops(&o, geom, epi, stream);
-}
-
-extern "C" int bcos_tapconv_presplit(const float* a, const float* wt, const void* wt3, const bcos_tapconv_geom* geom,
-                                     const bcos_epilogue* epi, void* stream) {
-    bcos_operands o = {a, nullptr, wt, wt3, nullptr, BCOS_CONTRACT_DEFAULT, nullptr, nullptr};
-    return bcos_tapconv_ops(&o, geom, epi, stream);
-}
-
-// ---- the dispatch of bcos_tapconv_ops, in stages: validate -> (batch chunks) -> resolve -> choose_route -> launch_route.  The two queries
-// (bcos_tapconv_fuses_image_range, bcos_tapconv_route_query) run the same stages and stop ahead of the launch.
-namespace {
-struct RouteEntry { const char* name; int fam, bm, bn; int (*launch)(const void*, int, hipStream_t); };
-#define BCOS_TC_X_ROW(name, fam, bm, bn) {#name, fam, bm, bn, bcos_tc_##name},
-const RouteEntry ROUTES[ROUTE_COUNT] = {BCOS_TC_ROUTES(BCOS_TC_X_ROW) {"skinny", -1, 0, 0, nullptr}};
-struct Route { int id, ch_pass; };      // ROUTE_*; ch_pass: input channels per pass of ROUTE_skinny, 0 otherwise
-struct Call { bcos_operands ops; bcos_tapconv_geom g; bcos_epilogue e; };
-
-inline int contraction_mode(const bcos_operands& o) { return o.contraction == BCOS_CONTRACT_DEFAULT ? g_contraction_mode.load(std::memory_order_relaxed) : o.contraction - 1; }
-
-// stage 1: the argument checks.  *gn receives the geometry with its default pitches filled in.
-int validate(const bcos_operands* ops, const bcos_tapconv_geom* geom, const bcos_epilogue* epi, bcos_tapconv_geom* gn) {
-    if (!ops || !geom || !epi) return bcos_set_error(BCOS_E_INVAL, "bcos_tapconv: NULL argument");
-    if (!ops->a || !ops->wt) return bcos_set_error(BCOS_E_INVAL, "bcos_tapconv: NULL operand");
-    if (ops->contraction < 0 || ops->contraction > BCOS_CONTRACT_F16X2)
-        return bcos_set_error(BCOS_E_INVAL, "bcos_tapconv: bad contraction selector");
-    const bcos_tapconv_geom& g = *geom;
-    if (g.N <= 0 || g.H <= 0 || g.W <= 0 || g.C <= 0 || g.P <= 0 || g.Q <= 0 || g.TH <= 0 || g.TW <= 0 ||
-        g.Cout <= 0 || g.OH <= 0 || g.OW <= 0)
-        return bcos_set_error(BCOS_E_INVAL, "bcos_tapconv: non-positive dimension");
-    if (g.C % 4 != 0) return bcos_set_error(BCOS_E_INVAL, "bcos_tapconv: C must be a multiple of 4");
-    if ((reinterpret_cast<uintptr_t>(ops->a) | reinterpret_cast<uintptr_t>(ops->wt)) & 15)
-        return bcos_set_error(BCOS_E_INVAL, "bcos_tapconv: operands must be 16-byte aligned");
-    if ((int64_t)g.N * g.P * g.Q >= (int64_t)1 << 31) return bcos_set_error(BCOS_E_NOSUP, "bcos_tapconv: more than 2^31 rows");
-    if (!epi->out && !epi->out2 && !epi->scale_out) return bcos_set_error(BCOS_E_INVAL, "bcos_tapconv: no output buffer");
-    if (epi->max_out < 0) return bcos_set_error(BCOS_E_INVAL, "bcos_tapconv: negative max_out");
-    if ((epi->flags & BCOS_EPI_MUL_FROM_ACT) && (!epi->mul || !epi->mul_norm || (epi->flags & BCOS_EPI_GATE2_FROM_MUL)))
-        return bcos_set_error(BCOS_E_INVAL, "bcos_tapconv: BCOS_EPI_MUL_FROM_ACT needs mul and mul_norm and excludes GATE2_FROM_MUL");
-    if (epi->max_out > 1) {
-        if ((epi->max_out != 2 && epi->max_out != 4) || g.Cout % 4 != 0)
-            return bcos_set_error(BCOS_E_NOSUP, "bcos_tapconv: fused MaxOut needs max_out in {2, 4} and Cout % 4 == 0");
-        if (epi->addend || epi->mul || epi->mul2 || epi->gate2 || epi->relu_gate || epi->out2 || epi->ch_scale || epi->ch_shift ||
-            epi->relu || epi->out_absmax || epi->out2_absmax || (epi->flags & ~(BCOS_EPI_FORCE_POW | BCOS_EPI_UNIT_NORM_W)))
-            return bcos_set_error(BCOS_E_NOSUP, "bcos_tapconv: fused MaxOut supports bias, the B-cos scale, out, scale_out and norm_out only");
-        if ((reinterpret_cast<uintptr_t>(epi->scale_out) & 15))
-            return bcos_set_error(BCOS_E_INVAL, "bcos_tapconv: scale_out must be 16-byte aligned");
-    }
-    if (epi->a_sumsq && epi->bcos_mode == BCOS_NONE)
-        return bcos_set_error(BCOS_E_INVAL, "bcos_tapconv: a_sumsq belongs to a B-cos launch (bcos_mode != BCOS_NONE)");
-    if ((epi->row_scale || epi->a_sumsq) && (g.groups > 1 || g.out_cgroup != 0))
-        return bcos_set_error(BCOS_E_NOSUP, "bcos_tapconv: row_scale / a_sumsq exclude grouped and depth-to-space launches");
-    if (epi->addend_sub < 0 || (epi->addend_sub > 1 && (!epi->addend || g.out_cgroup != 0 || g.groups > 1 || epi->bcos_mode != BCOS_NONE)))
-        return bcos_set_error(BCOS_E_INVAL, "bcos_tapconv: addend_sub > 1 needs an addend and a plain gradient launch (bcos_mode BCOS_NONE, "
-                                            "no out_cgroup, no groups)");
-    // the last row/col written must be inside the output tensor
-    if ((g.P - 1) * g.out_sh + g.out_h0 >= g.OH || (g.Q - 1) * g.out_sw + g.out_w0 >= g.OW || g.out_h0 < 0 || g.out_w0 < 0)
-        return bcos_set_error(BCOS_E_INVAL, "bcos_tapconv: output mapping outside [OH,OW]");
-    const int G = g.groups > 1 ? g.groups : 1;
-    if (g.groups < 0 || g.groups > 65535) return bcos_set_error(BCOS_E_INVAL, "bcos_tapconv: bad group count");
-    if (G > 1 && (g.out_cgroup != 0 || epi->max_out > 1 || epi->out_absmax || epi->out2_absmax))
-        return bcos_set_error(BCOS_E_NOSUP, "bcos_tapconv: grouped launches exclude out_cgroup, fused MaxOut and *_absmax");
-    if (g.out_cgroup != 0) {     // depth to space: columns = (output parity class, channel)
-        if (g.out_cgroup < 0 || g.out_cgroup % 4 != 0 || g.out_sh <= 0 || g.out_sw <= 0 || g.out_h0 != 0 || g.out_w0 != 0 ||
-            g.Cout != g.out_sh * g.out_sw * g.out_cgroup || g.P * g.out_sh > g.OH || g.Q * g.out_sw > g.OW ||
-            (g.out_pitch != 0 && g.out_pitch < g.out_cgroup))
-            return bcos_set_error(BCOS_E_INVAL, "bcos_tapconv: out_cgroup needs Cout == out_sh * out_sw * out_cgroup, out_cgroup % 4 == 0, "
-                                                "zero output offsets, P * out_sh <= OH, Q * out_sw <= OW and out_pitch >= out_cgroup");
-        if (epi->max_out > 1 || epi->out_absmax || epi->out2_absmax || epi->norm_out || epi->bias || epi->ch_scale || epi->ch_shift ||
-            (epi->flags & BCOS_EPI_MUL_FROM_ACT) || epi->bcos_mode != BCOS_NONE)
-            return bcos_set_error(BCOS_E_NOSUP, "bcos_tapconv: out_cgroup launches are plain gradient launches (addend / mul / mul2 / "
-                                                "gate2 / out / out2 only)");
-    }
-    *gn = g;
-    if (gn->a_pitch == 0) gn->a_pitch = G * g.C;
-    if (gn->out_pitch == 0) gn->out_pitch = g.out_cgroup > 0 ? g.out_cgroup : G * g.Cout;
-    if (gn->norm_pitch == 0) gn->norm_pitch = G;
-    if (gn->a_pitch % 4 != 0 || gn->a_pitch < G * g.C) return bcos_set_error(BCOS_E_INVAL, "bcos_tapconv: bad a_pitch");
-    if (epi->max_out > 1 && g.out_pitch == 0) gn->out_pitch = g.Cout / epi->max_out;
-    if (g.out_cgroup == 0 && gn->out_pitch < G * g.Cout / (epi->max_out > 1 ? epi->max_out : 1))
-        return bcos_set_error(BCOS_E_INVAL, "bcos_tapconv: bad out_pitch");
-    if (gn->norm_pitch < G) return bcos_set_error(BCOS_E_INVAL, "bcos_tapconv: norm_pitch smaller than the group count");
-    return BCOS_OK;
-}
-
-// How many images of a validated call go into one launch (g.N: all of them).  The split-bf16 path addresses its operands through
-// 32-bit buffer offsets: keep each launch below 2 GiB of A by splitting the batch (every tensor of the call is per-image separable);
-// a call that cannot be split falls back to fp32 MFMA in select_operands.
-int images_per_launch(const bcos_operands& ops, const bcos_tapconv_geom& g) {
-    const int G = g.groups > 1 ? g.groups : 1, Ktot = g.TH * g.TW * g.C;
-    const int64_t img_bytes = (int64_t)g.H * g.W * g.a_pitch * 4, a_bytes = img_bytes * g.N, wt_bytes = (int64_t)G * g.Cout * Ktot * 4;
-    // (BCOS_OPT_SPLIT_LIMIT: tests lower the chunking threshold to drive this path with small tensors)
-    const int64_t chunk_lim = bcos_option(BCOS_OPT_SPLIT_LIMIT);
-    const bool split = contraction_mode(ops) >= 1 && a_bytes >= chunk_lim && g.N > 1 && img_bytes < chunk_lim && wt_bytes < ((int64_t)1 << 31);
-    return split ? (int)((chunk_lim - 1) / img_bytes) : g.N;
-}
-
-// images [n0, n0 + per) of a call (fewer in the last chunk) as a call of their own: every per-image pointer moved to image n0
-Call chunk_of(const bcos_operands& ops, const bcos_tapconv_geom& g, const bcos_epilogue& epi, int n0, int per) {
-    Call c = {ops, g, epi};
-    bcos_epilogue& e2 = c.e;
-    c.g.N = g.N - n0 < per ? g.N - n0 : per;
-    const int64_t opix = (int64_t)n0 * g.OH * g.OW;
-    const float** cin[] = {&e2.addend, &e2.mul, &e2.mul2, &e2.gate2, &e2.relu_gate, &e2.rowadd};      // indexed like out
-    for (const float** q : cin) if (*q) *q += opix * g.out_pitch;
-    if (const int sb = e2.addend_sub; e2.addend && sb > 1)      // subsampled addend: its own image size
-        e2.addend = epi.addend + (int64_t)n0 * ((g.OH + sb - 1) / sb) * ((g.OW + sb - 1) / sb) * g.out_pitch;
-    float** cout[] = {&e2.out, &e2.out2, &e2.scale_out};
-    for (float** q : cout) if (*q) *q += opix * g.out_pitch;
-    if (e2.norm_out) e2.norm_out += opix * g.norm_pitch;
-    const float** cpx[] = {&e2.mul_norm, &e2.row_scale, &e2.a_sumsq, &e2.rowadd_scale};      // one value per output pixel
-    for (const float** q : cpx) if (*q) *q += opix;
-    if (e2.out_absmax) e2.out_absmax += opix;
-    if (e2.out2_absmax) e2.out2_absmax += opix;
-    if (e2.out_imgmax) e2.out_imgmax += n0;
-    if (e2.out_imgmin_c) e2.out_imgmin_c += n0;
-    bcos_operands& o2 = c.ops;
-    o2.a = ops.a + (int64_t)n0 * g.H * g.W * g.a_pitch;
-    if (o2.a_absmax) o2.a_absmax += (int64_t)n0 * g.H * g.W;
-    if (o2.a_imgmax) o2.a_imgmax += n0;          // (per-image maxima are indexed by the chunk's local image index)
-    if (o2.a_imgmin) o2.a_imgmin += n0;
-    if (o2.a_imgmin_c) o2.a_imgmin_c += n0;
-    return c;
-}
-
-// resolve, part 1: the contraction loop's operands -- x3, the pre-split weight image, the split-f16 decision (p.h2 and its side tensors) -- and the 2 GiB limits
-void select_operands(const bcos_operands& ops, KArgs& p) {
-    const bcos_tapconv_geom& g = p.g;
-    const int mode = contraction_mode(ops), G = g.groups > 1 ? g.groups : 1;
-    const int64_t a_bytes = (int64_t)g.H * g.W * g.a_pitch * 4 * g.N, wt_bytes = (int64_t)G * g.Cout * p.Ktot * 4;
-    const int64_t lim = (int64_t)1 << 31;
-    p.x3 = (mode >= 1 && a_bytes < lim && wt_bytes < lim) ? 1 : 0;
-    p.a_bytes = (unsigned)(a_bytes < lim ? a_bytes : 0);
-    p.wt_bytes = (unsigned)(wt_bytes < lim ? wt_bytes : 0);
-    const int64_t w3b = split_bytes(G * g.Cout, p.Ktot);
-    // (grouped launches index the image by global weight row: a group's rows must start on a 32-row fragment tile)
-    const bool unit_w = (p.e.flags & BCOS_EPI_UNIT_NORM_W) != 0;     // norms come from the fp32 weight rows in the staging registers
-    const void* wt3 = ops.wt_bf16x3;
-    p.wt3 = (p.x3 && !unit_w && wt3 && w3b < lim && !(reinterpret_cast<uintptr_t>(wt3) & 15) && (G == 1 || g.Cout % 32 == 0)) ? wt3 : nullptr;
-    p.wt3_bytes = (unsigned)(w3b < lim ? w3b : 0);
-    p.h2 = 0;
-    p.a_absmax = p.a_imgmax = p.a_imgmin = p.a_imgmin_c = nullptr;
-    p.wt2 = nullptr, p.wt2_cinv = nullptr;
-    p.absmax_bytes = p.wt2_bytes = 0;
-    const int64_t w2b = h2_image_bytes(g.Cout, p.Ktot), pixb = (int64_t)g.N * g.H * g.W * 4;
-    // below K = 256 a launch is HBM-bound and the bf16x3 loop (no operand maxima to produce) is as fast, unless the caller
-    // insists on f16x2; at K = 256 the six bf16 products still occupy a third of the SIMD cycles (14^2 layers of ResNet-50:
-    // -12 % per launch with three f16 products).  The stem's K is all taps over 8 channels: compute-bound at any K.
-    const bool h2_pays = p.Ktot >= 256 || (g.C <= 16 && p.Ktot >= 128) || ops.contraction == BCOS_CONTRACT_F16X2;
-    if (mode == 2 && G == 1 && h2_pays && !unit_w && p.x3 && ops.a_absmax && ops.wt_f16x2 && w2b < lim && pixb < lim &&
-        !(reinterpret_cast<uintptr_t>(ops.wt_f16x2) & 15)) {
-        p.h2 = 1;
-        p.a_absmax = ops.a_absmax;
-        // BCOS_OPT_PATCH = 0 (development / test switch): no per-image range, i.e. per-row scales everywhere -- the per-tap loops as they were
-        if (bcos_option(BCOS_OPT_PATCH) != 0) {
-            p.a_imgmax = ops.a_imgmax;
-            p.a_imgmin = ops.a_imgmax ? ops.a_imgmin : nullptr;
-            p.a_imgmin_c = (ops.a_imgmax && !ops.a_imgmin) ? ops.a_imgmin_c : nullptr;
-        }
-        p.absmax_bytes = (unsigned)pixb;
-        p.wt2 = ops.wt_f16x2;
-        p.wt2_bytes = (unsigned)w2b;
-        p.wt2_cinv = reinterpret_cast<const float*>(static_cast<const char*>(ops.wt_f16x2) + w2b);
-    }
-}
-
-// resolve, part 2: the specialised epilogue (tile_epilogue_fast) when the launch's feature set is one of the compiled kinds; sets p.epi_kind / p.out_bytes
-void select_epilogue_kind(KArgs& p) {
-    const bcos_tapconv_geom& g = p.g;
-    const bcos_epilogue& e = p.e;
-    p.epi_kind = 0, p.out_bytes = 0;
-    const int64_t obytes = (int64_t)g.N * g.OH * g.OW * g.out_pitch * 4;
-    const bool norm_l = e.bcos_mode != BCOS_NONE;
-    const bool off = bcos_option(BCOS_OPT_EPI_GENERIC) != 0;                // development / test switch
-    // (a row_scale rides in the inverse operand scale of the split-f16 loops; the other loops carry it through the general epilogue)
-    bool ok = !off && p.vec_ok && g.Cout % 4 == 0 && obytes < ((int64_t)1 << 31) && e.max_out <= 1 && e.out != nullptr && !e.col_scale && !(e.flags & BCOS_EPI_UNIT_NORM_W) &&
-              (!e.row_scale || p.h2) &&
-              !e.gate2 && !e.relu_gate && !(e.flags & (BCOS_EPI_NORM_ONLY | BCOS_EPI_FORCE_POW)) &&
-              ((reinterpret_cast<uintptr_t>(e.bias) | reinterpret_cast<uintptr_t>(e.ch_scale) | reinterpret_cast<uintptr_t>(e.ch_shift)) & 15) == 0;
-    int ef = 0;
-    if (norm_l) {
-        ok = ok && e.b == 2.0f && e.relu >= 0 && e.relu <= 2 && !e.mul && !e.mul2 && !e.out2 && !e.out2_absmax &&
-             !(e.flags & BCOS_EPI_MUL_FROM_ACT);
-        ef = (e.addend ? EF_ADDEND : 0) | (e.relu == 1 ? EF_RELU : 0) | (e.relu == 2 ? EF_GELU : 0) | (e.scale_out ? EF_SCALE_OUT : 0);
-    } else {
-        ok = ok && e.relu == 0 && !e.ch_scale && !e.ch_shift && !e.scale_out && (!e.mul2 || e.out2) &&
-             (!e.out2 || e.mul) && (!e.out2_absmax || e.out2);
-        // out2 is either ungated or gated by the low bit of mul (BCOS_EPI_GATE2_FROM_MUL): both are what the kinds compute
-        ef = (e.addend ? EF_ADDEND : 0) | (e.mul ? EF_MUL : 0) | (e.out2 ? EF_OUT2 : 0) | (e.mul2 ? EF_MUL2 : 0) |
-             ((e.flags & BCOS_EPI_MUL_FROM_ACT) ? EF_MULACT : 0) | (e.rowadd ? (EF_ROWADD | EF_ADDEND) : 0);
-        if (e.rowadd) ok = ok && e.rowadd_scale && e.addend_sub <= 1 && !(reinterpret_cast<uintptr_t>(e.rowadd) & 15) && g.out_cgroup == 0;
-        if (e.flags & BCOS_EPI_MUL_FROM_ACT)
-            ok = ok && ((reinterpret_cast<uintptr_t>(e.mul_csc) | reinterpret_cast<uintptr_t>(e.mul_csh)) & 15) == 0;
-    }
-    if (!ok) return;
-    const int* kinds = norm_l ? EPI_KINDS_FWD : EPI_KINDS_BWD;
-    for (int k = 0; k < N_EPI_KINDS; ++k)
-        if (kinds[k] == ef) { p.epi_kind = k + 1; p.out_bytes = (unsigned)obytes; break; }
-}
-
-// stage 2: the launch descriptor of one validated call (a chunk of it).  *fuses: does the launch fold the per-image range of its
-// out_absmax into out_imgmax / out_imgmin_c -- what bcos_tapconv_fuses_image_range answers, ahead of plan_launch's check of the pair.
-int resolve(const Call& c, KArgs& p, bool* fuses) {
-    const bcos_tapconv_geom& g = c.g;
-    const bcos_epilogue& e = c.e;
-    p.a = c.ops.a; p.wt = c.ops.wt; p.g = g; p.e = e;
-    p.M = g.N * g.P * g.Q;
-    p.PQ = g.P * g.Q;
-    p.Ktot = g.TH * g.TW * g.C;
-    p.cpt = g.C / 4;
-    p.nchunks = p.Ktot / 4;
-    p.nk = (p.nchunks + 7) / 8;
-    p.tiles_n = p.n_big = p.n_small = p.rows_big = 0;
-    p.uniform_tap = (g.C % BK == 0) ? 1 : 0;
-    p.lvl_off = 0;
-    p.lvl_on = bcos_option(BCOS_OPT_PATCH_LEVELS) != 0;
-    p.t2_bw = p.t2_nbx = p.t2_nb = p.t2_rows = 0;
-    select_operands(c.ops, p);
-    uintptr_t bits = 0;
-    const void* ptrs[] = {e.addend, e.mul, e.mul2, e.gate2, e.relu_gate, e.out, e.out2, e.scale_out};
-    for (const void* q : ptrs) bits |= reinterpret_cast<uintptr_t>(q);
-    p.vec_ok = ((bits & 15) == 0 && g.out_pitch % 4 == 0) ? 1 : 0;
-    if (g.out_cgroup > 0 && !p.vec_ok)
-        return bcos_set_error(BCOS_E_INVAL, "bcos_tapconv: out_cgroup needs 16-byte addressable epilogue tensors");
-    select_epilogue_kind(p);
-    if (e.rowadd && (p.epi_kind == 0 || (e.bcos_mode != BCOS_NONE)))
-        return bcos_set_error(BCOS_E_NOSUP, "bcos_tapconv: rowadd / rowadd_scale belong to a plain gradient launch that takes a specialised epilogue "
-                                            "(16-byte addressable tensors < 2 GiB, Cout % 4 == 0, no mul / out2 / addend_sub): use bcos_patch_norm_bwd_add");
-    // per-image range of the emitted maxima (bcos_epilogue.out_imgmax / out_imgmin_c): folded into the specialised epilogues only, for
-    // launches whose tiles span at most 16 images (256 rows at >= 19 rows per image), plain output mapping, one group
-    *fuses = p.epi_kind > 0 && e.out_absmax && g.out_cgroup == 0 && g.groups <= 1 && (int64_t)g.P * g.Q >= 19;
-    return BCOS_OK;
-}
-
-// stage 3: which launcher a resolved launch takes -- a function of the descriptor (geometry, epilogue, p.h2 / p.a_imgmax) and the
-// option table; launches nothing
-#define BCOS_TC_GO(name) Route{ROUTE_##name, 0}
-Route choose_route(const KArgs& p) {
-    const bcos_tapconv_geom& g = p.g;
-    const bcos_epilogue& e = p.e;
-    const int G = g.groups > 1 ? g.groups : 1;
-    const int64_t M64 = p.M;
-    const bool narrow = g.Cout <= 8 && G == 1 && !e.out_absmax && !e.out2_absmax && e.max_out <= 1 && e.addend_sub <= 1 && !e.row_scale && !e.a_sumsq && !e.rowadd;
-    if (const int ch_pass = narrow ? bcos_skinny_ch_pass(g, e) : 0) return Route{ROUTE_skinny, ch_pass};
-    if (p.h2) {
-        // staging of the split-f16 loop: LDS-DMA (tile_body_d, default) or registers (tile_body_h2: BCOS_H2_LOOP=regs); same bits
-        const bool dma = bcos_option(BCOS_OPT_H2_LOOP) == 0;
-        {
-            // multi-tap launches over an LDS-resident input patch (tile_body_p).  The choice depends on the layer's geometry alone,
-            // never on the batch: the patch loop rounds differently from the per-tap loops (one operand scale per image), and an
-            // image's bits must not depend on how many images share its launch.  (BCOS_OPT_PATCH = 0: select_operands passed no p.a_imgmax on.)
-            const int ntaps = g.TH * g.TW;
-            const bool geom_ok = ((ntaps == 9 && g.TH == 3) || (ntaps == 16 && g.TH == 4)) && g.C % X3_BK == 0 && g.in_sh == 1 && g.in_sw == 1 &&
-                                 g.dstep_h == 1 && g.dstep_w == 1 && g.a_pitch >= g.C;
-            if (dma && geom_ok && p.a_imgmax && !e.row_scale && !e.a_sumsq) {      // (the patch kernels compile those two out)
-                if (ntaps == 16) {
-                    if (g.Cout <= 32 && g.in_sh == 1) return BCOS_TC_GO(p2_256x32_t16);
-                } else {
-                if (g.Cout > 128 && g.Cout <= 256 && patch_fits(g, 128, 256, 256) && bcos_option(BCOS_OPT_PATCH_WIDE)) return BCOS_TC_GO(p_128x256_a);
-                if (g.Cout > 64 && patch_fits(g, 128, 256, 256)) return BCOS_TC_GO(p_128x128_a);
-                if (g.Cout > 64 && patch_fits(g, 128, 256, 448)) return BCOS_TC_GO(p_128x128_b);
-                if (g.Cout > 64 && patch_fits(g, 128, 384, 320)) return BCOS_TC_GO(p_128x128_c);
-                if (g.Cout > 32 && g.Cout <= 64 && patch_fits(g, 256, 640, 640)) return BCOS_TC_GO(p_256x64_a);
-                // wider images (112^2: the 3 x 3 stem convolutions of the CLIP ResNets): 8 x 32 blocks.  (At 56^2 the linear tiles win,
-                // 224 against 253 us: the blocks leave an eighth of the rows empty there.)
-                if (g.Cout > 32 && g.Cout <= 64 && g.in_sh == 1 && g.Q > 64) return BCOS_TC_GO(p2_256x64_b32);
-                if (g.Cout > 8 && g.Cout <= 32 && g.in_sh == 1 && g.Q > 64) return BCOS_TC_GO(p2_256x32_t9);
-                }
-            }
-        }
-        if (g.Cout > 64 && dma && bcos_option(BCOS_OPT_H2_TILE) == 0) {
-            // FEW-ROW launches (M <= a few hundred rows: the pooled token of CLIP's attention pool at batch 256 -- 2 row tiles --, small
-            // batches through every head): with 128- or 256-column tiles they occupy a handful of CUs and run at the latency of ONE
-            // workgroup's K loop (256 x 2048 -> 1024: 8 workgroups, 111 us against 28 for the vendor's GEMM).  Narrower
-            // column tiles multiply the workgroups -- 64 or 32 columns each, as many as it takes to put a workgroup on half the CUs -- at
-            // no cost in bits (an output element's K order does not depend on its tile).
-            const int64_t tm = (M64 + 127) / 128;
-            const int64_t t128 = tm * ((g.Cout + 127) / 128);
-            if (t128 < 64) {
-                if (tm * ((g.Cout + 63) / 64) >= 96 || g.Cout <= 128) return BCOS_TC_GO(d_128x64);
-                return BCOS_TC_GO(d_128x32);
-            }
-        }
-        if (g.Cout > 64) {
-            // 128 x 256 tiles stage half the A bytes per MFMA; they pay when they do not cost an extra round of tiles
-            // (measured on the ResNet-50 shapes: M = 50176, N = 256: -3 %; M = 12544, N = 512: +17 % -> stays 128 x 128)
-            const int64_t force = bcos_option(BCOS_OPT_H2_TILE);      // development switch: 1 = 128 x 128, 2 = 128 x 256
-            const int64_t tm = (M64 + 127) / 128;
-            const int64_t t1 = tm * ((g.Cout + 127) / 128), t2 = tm * ((g.Cout + 255) / 256);
-            // (a finer cost model -- a wide tile = 1.75 narrow ones, which moves M = 200 704 with N = 256 / 512 and M = 50 176 with
-            // N = 1024, K = 512 to wide tiles -- wins 11-18 % on those launches timed one by one and loses 0.1 ms on the step, where
-            // consecutive launches overlap their tails: not adopted)
-            // rounds of tiles, a wide tile priced at BCOS_OPT_H2_WIDE_COST / 4 narrow ones (8 = two, the model of rounds 2-3; the wide
-            // tile shares the A operand's DMA and split between its halves, so 7 is nearer what the layers measure)
-            const int64_t wc = bcos_option(BCOS_OPT_H2_WIDE_COST);
-            const int64_t c1 = 4 * ((t1 + SLOTS - 1) / SLOTS), c2 = wc * ((t2 + SLOTS - 1) / SLOTS);
-            bool wide = g.Cout > 128 && (c2 < c1 || (c2 == c1 && (wc < 8 || p.Ktot >= 1024)));
-            if (force) wide = g.Cout > 128 && force == 2;
-            // 129 ... 192 columns (the 192-wide linears of the SimpleViTs: to_out, linear2, their gradients): ONE tile of 192 columns
-            // (six accumulator tiles per wave) instead of 128 + a half-empty second 128
-            if (dma && g.Cout > 128 && g.Cout <= 192 && !force) return BCOS_TC_GO(d_128x192);
-            // multiples of 192 that are not multiples of 256 (the 576-wide to_qkv of the SimpleViTs: 3 x 192 exactly, against 5 x 128 with
-            // 64 empty columns or 3 x 256 with 192): whole 192-column tiles -- ViT-Ti batch 512 forward+explanation 18.26 -> 17.97 ms per step
-            // in three same-node pairs (round 5); 768 = 4 x 192 against 3 x 256: no gain, stays on the 256-column tiles.  Bits unchanged.
-            if (dma && g.Cout % 192 == 0 && g.Cout % 256 != 0 && g.Cout <= 1152 && !force) return BCOS_TC_GO(d_128x192);
-            if (wide) return dma ? BCOS_TC_GO(d_128x256) : BCOS_TC_GO(h2_128x256);
-            return dma ? BCOS_TC_GO(d_128x128) : BCOS_TC_GO(h2_128x128);
-        }
-        if (g.Cout > 32) {
-            // 256 x 64 tiles (four waves of 64 x 64: the A operand's split, its LDS image and the per-tile prologue / epilogue
-            // latencies are shared by twice the matrix instructions of a 128 x 64 tile) from two rounds of tiles on.  Same-node
-            // A/B on the ResNet-50 step at batch 256 (M = 802 816): 3x3 64 -> 64 gradient 1.03 -> 0.90 ms, 256 -> 64 gradient
-            // 1.21 -> 1.13 ms, stem forward 1.05 -> 1.01 ms, the forward launches -1 %.  Results are identical bit for bit (same
-            // K walk, same product order per accumulator).
-            const bool tall = bcos_option(BCOS_OPT_H2_TALL) != 0;       // development switch: 0 keeps the 128-row tiles
-            const int64_t tall_min = bcos_option(BCOS_OPT_H2_TALL_MIN);     // default 2 * 256 * SLOTS (batch 128, M = 401 408: +0.4 % per step; M = 200 704: neutral)
-            if (M64 >= tall_min && tall) return dma ? BCOS_TC_GO(d_256x64) : BCOS_TC_GO(h2_256x64);
-            return dma ? BCOS_TC_GO(d_128x64) : BCOS_TC_GO(h2_128x64);
-        }
-        {   // 256 x 32 tiles likewise (the depth-to-space stem gradient, M = 3.2 M: 1.29-1.38 -> 1.17-1.20 ms in a same-node A/B)
-            if (M64 >= 2 * 256 * SLOTS && bcos_option(BCOS_OPT_H2_TALL)) return dma ? BCOS_TC_GO(d_256x32) : BCOS_TC_GO(h2_256x32);
-        }
-        return dma ? BCOS_TC_GO(d_128x32) : BCOS_TC_GO(h2_128x32);
-    }
-    if (g.Cout > 64) {
-        // few-row launches (see the split-f16 branch above): narrower column tiles put a workgroup on more CUs; same bits
-        const int64_t tm = (M64 + 127) / 128;
-        if (G == 1 && tm * ((g.Cout + 127) / 128) < 64 && bcos_option(BCOS_OPT_H2_TILE) == 0)
-            return (tm * ((g.Cout + 63) / 64) >= 96 || g.Cout <= 128) ? BCOS_TC_GO(cfg_128x64) : BCOS_TC_GO(cfg_128x32);
-        return BCOS_TC_GO(cfg_128x128);
-    }
-    if (g.Cout > 32) return BCOS_TC_GO(cfg_128x64);
-    return BCOS_TC_GO(cfg_128x32);
-}
-#undef BCOS_TC_GO
-
-// stage 4: the launcher of the route, or the narrow-output kernel
-int launch_route(const Route& r, const KArgs& p, hipStream_t s) {
-    if (r.id == ROUTE_skinny) return bcos_skinny_launch(p.a, p.wt, p.g, p.e, s);
-    return ROUTES[r.id].launch(&p, p.e.bcos_mode != BCOS_NONE ? 1 : 0, s);
-}
-
-// resolve -> the check of the out_imgmax / out_imgmin_c pair -> choose_route: everything of one launch but the launch
-int plan_launch(const Call& c, KArgs& p, Route* r) {
-    bool fuses = false;
-    const int rc = resolve(c, p, &fuses);
-    if (rc != BCOS_OK) return rc;
-    if ((c.e.out_imgmax || c.e.out_imgmin_c) && (!c.e.out_imgmax || !c.e.out_imgmin_c || !fuses))
-        return bcos_set_error(BCOS_E_NOSUP, "bcos_tapconv: out_imgmax / out_imgmin_c come as a pair, with out_absmax, and only for launches "
-                                            "bcos_tapconv_fuses_image_range() answers 1 for");
-    *r = choose_route(p);
-    return BCOS_OK;
-}
-}  // namespace
-
-extern "C" int bcos_tapconv_ops(const bcos_operands* ops, const bcos_tapconv_geom* geom, const bcos_epilogue* epi, void* stream) {
-    bcos_tapconv_geom g;
-    int rc = validate(ops, geom, epi, &g);
-    if (rc != BCOS_OK) return rc;
-    const int per = images_per_launch(*ops, g);
-    for (int n0 = 0; n0 < g.N; n0 += per) {
-        KArgs p; Route r;
-        rc = plan_launch(chunk_of(*ops, g, *epi, n0, per), p, &r);
-        if (rc == BCOS_OK) rc = launch_route(r, p, reinterpret_cast<hipStream_t>(stream));
-        if (rc != BCOS_OK) return rc;
-    }
-    return BCOS_OK;
-}
-
-// 1: a bcos_tapconv_ops call with these arguments folds the per-image range of its out_absmax into bcos_epilogue.out_imgmax / out_imgmin_c
-// itself; 0: it does not (general epilogue, depth-to-space or grouped launch, fewer than 19 rows per image, no out_absmax) and rejects
-// the two fields; < 0: the arguments are invalid anyway.  Nothing is launched: validate and resolve, as the launch runs them.
-extern "C" int bcos_tapconv_fuses_image_range(const bcos_operands* ops, const bcos_tapconv_geom* geom, const bcos_epilogue* epi) {
-    bcos_tapconv_geom g;
-    int rc = validate(ops, geom, epi, &g);
-    if (rc != BCOS_OK) return rc;
-    const int per = images_per_launch(*ops, g);
-    // (chunks differ in their image count alone, which decides the answer only through the 2 GiB limits: 1 if any chunk folds)
-    for (int n0 = 0; n0 < g.N; n0 += per) {
-        KArgs p; bool fuses = false;
-        rc = resolve(chunk_of(*ops, g, *epi, n0, per), p, &fuses);
-        if (rc != BCOS_OK) return rc;
-        if (fuses) return 1;
-    }
-    return 0;
-}
-
-extern "C" int bcos_tapconv_route_query(const bcos_operands* ops, const bcos_tapconv_geom* geom, const bcos_epilogue* epi, bcos_tapconv_route* out) {
-    if (!out) return bcos_set_error(BCOS_E_INVAL, "bcos_tapconv_route_query: NULL result");
-    *out = bcos_tapconv_route{-1, 0, 0, 0, 0, 0, 0, 0};
-    bcos_tapconv_geom g;
-    int rc = validate(ops, geom, epi, &g);
-    if (rc != BCOS_OK) return rc;
-    const int per = images_per_launch(*ops, g);
-    KArgs p; Route r;
-    rc = plan_launch(chunk_of(*ops, g, *epi, 0, per), p, &r);      // (the first chunk's route)
-    if (rc != BCOS_OK) return rc;
-    const RouteEntry& row = ROUTES[r.id];
-    const int chunks = (g.N + per - 1) / per;
-    if (r.id == ROUTE_skinny) *out = bcos_tapconv_route{r.id, 0, 0, BCOS_LOOP_F32, 0, 0, chunks, r.ch_pass};      // (its own plain epilogue)
-    else *out = bcos_tapconv_route{r.id, p.epi_kind, p.e.bcos_mode != BCOS_NONE ? 1 : 0, family_loop(row.fam, p), row.bm, row.bn, chunks, 0};
-    return BCOS_OK;
-}
-
-extern "C" const char* bcos_tapconv_route_name(int route) { return route >= 0 && route < ROUTE_COUNT ? ROUTES[route].name : nullptr; }
-extern "C" int bcos_tapconv_route_count(void) { return ROUTE_COUNT; }
-extern "C" int bcos_tapconv_epilogue_kinds(void) { return N_EPI_KINDS; }
-
-extern "C" int bcos_tapconv_group(const float* a, const float* const* wts, const bcos_tapconv_geom* geoms,
-                                  const bcos_epilogue* epis, int count, void* stream) {
-    if (!a || !wts || !geoms || !epis || count <= 0) return bcos_set_error(BCOS_E_INVAL, "bcos_tapconv_group: bad argument");
-    const int fused = bcos_try_skinny_group(a, wts, geoms, epis, count, reinterpret_cast<hipStream_t>(stream));
-    if (fused < 0) return fused;
-    if (fused == 1) return BCOS_OK;
-    for (int i = 0; i < count; ++i) {
-        const int rc = bcos_tapconv(a, wts[i], &geoms[i], &epis[i], stream);
-        if (rc != BCOS_OK) return rc;
-    }
-    return BCOS_OK;
-}
 #endif  // BCOS_TC_IN(0)

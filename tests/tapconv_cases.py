@@ -14,7 +14,7 @@ from dataclasses import dataclass
 
 import torch
 
-N_KINDS = 8          # specialised epilogue kinds per direction (csrc/bcos_tapconv.hip: N_EPI_KINDS; bcos_tapconv_epilogue_kinds())
+N_KINDS = 8          # specialised epilogue kinds per direction (csrc/bcos_tapconv_plan.h: N_EPI_KINDS; bcos_tapconv_epilogue_kinds())
 
 EPI_NORM_ONLY, EPI_FORCE_POW, EPI_SCALE_GATE_LSB, EPI_GATE2_FROM_MUL, EPI_MUL_FROM_ACT, EPI_UNIT_NORM_W = 1, 2, 4, 8, 16, 32
 
@@ -22,7 +22,7 @@ EPI_NORM_ONLY, EPI_FORCE_POW, EPI_SCALE_GATE_LSB, EPI_GATE2_FROM_MUL, EPI_MUL_FR
 @dataclass(frozen=True)
 class Epi:
     """An epilogue feature set.  `kind`: the epilogue kind the dispatcher is expected to pick (0 = general, k = specialised kind k
-    of the direction: csrc/bcos_tapconv.hip EPI_KINDS_FWD / EPI_KINDS_BWD, in their order)."""
+    of the direction: csrc/bcos_tapconv_plan.h EPI_KINDS_FWD / EPI_KINDS_BWD, in their order)."""
     name: str
     kind: int
     bcos_mode: int = 0            # 0 plain / gradient launch, 1 BCOS_CONV_EPS, 2 BCOS_LINEAR_EPS
@@ -91,7 +91,7 @@ GENERAL = Epi("g_b2p5", 0, bcos_mode=1, b=2.5, scale_out=True, norm_out=True, bi
 GENERAL_BWD = Epi("g_gate2", 0, mul=True, out2=True, mul2=True, gate2=True)            # the general epilogue of a plain / gradient launch
 ALL_KINDS = FWD_KINDS + BWD_KINDS + [GENERAL, GENERAL_BWD]
 
-# the reasons the dispatcher falls back to the general epilogue for (csrc/bcos_tapconv.hip: select_epilogue_kind, the "specialised epilogue" stage of the dispatch);
+# the reasons the dispatcher falls back to the general epilogue for (csrc/bcos_tapconv_dispatch.hip: select_epilogue_kind, the "specialised epilogue" stage of the dispatch);
 # spread over the routes, one or two per route
 GENERAL_REASONS = [
     Epi("g_force_pow", 0, bcos_mode=1, flags=EPI_FORCE_POW, scale_out=True),
@@ -297,14 +297,14 @@ ROUTES = [
 UNREACHABLE = (
     [("skinny", 1, k, "csrc/bcos_skinny.hip skinny_decide: `if (e.bcos_mode != BCOS_NONE || ...) return false` -- a B-cos launch never takes the narrow kernel")
      for k in range(0, N_KINDS + 1)] +
-    [("skinny", 0, k, "csrc/bcos_tapconv.hip bcos_tapconv_route_query: the narrow kernel has its own plain epilogue; the query reports epi_kind 0 for it")
+    [("skinny", 0, k, "csrc/bcos_tapconv_dispatch.hip bcos_tapconv_route_query: the narrow kernel has its own plain epilogue; the query reports epi_kind 0 for it")
      for k in range(1, N_KINDS + 1)])
 
 # features the dispatcher keeps off a launcher family (asked per feature, not per kind): (route prefix, epilogue set, where the launch goes instead, source)
 FEATURE_DETOURS = [
-    ("p128a", F_ROW_SCALE, "d_128x64", "csrc/bcos_tapconv.hip choose_route: `if (dma && geom_ok && p.a_imgmax && !e.row_scale && !e.a_sumsq)`"),
+    ("p128a", F_ROW_SCALE, "d_128x64", "csrc/bcos_tapconv_dispatch.hip choose_route: `if (dma && geom_ok && p.a_imgmax && !e.row_scale && !e.a_sumsq)`"),
     ("p128a", B_ROW_SCALE, "d_128x64", "the same condition: the patch kernels compile row_scale out"),
-    ("d192_132", G_UNIT_NORM_W, "cfg_128x128", "csrc/bcos_tapconv.hip select_operands: `if (mode == 2 && G == 1 && h2_pays && !unit_w ...` -- BCOS_EPI_UNIT_NORM_W runs on the fp32 / bf16x3 loops"),
+    ("d192_132", G_UNIT_NORM_W, "cfg_128x128", "csrc/bcos_tapconv_dispatch.hip select_operands: `if (mode == 2 && G == 1 && h2_pays && !unit_w ...` -- BCOS_EPI_UNIT_NORM_W runs on the fp32 / bf16x3 loops"),
 ]
 
 
@@ -324,7 +324,7 @@ def bcos_forward_errors(y, s, n, y64, s64, n64, norm_y, norm_s, tiny=1e-30):
 
 
 def loops_of(route_name):
-    """The contraction loops a launcher can run (csrc/bcos_tapconv.hip family_loop: launch_cfg picks among three, the others instantiate one)."""
+    """The contraction loops a launcher can run (csrc/bcos_tapconv_plan.h family_loop: launch_cfg picks among three, the others instantiate one)."""
     if route_name == "skinny":
         return ["f32"]
     fam = route_name.split("_")[0]
@@ -332,7 +332,7 @@ def loops_of(route_name):
 
 
 def rejected(r, e):
-    """Pairs bcos_tapconv_ops' argument validation (csrc/bcos_tapconv.hip: validate) rejects (include/bcos_hip.h): nothing is asked of them."""
+    """Pairs bcos_tapconv_ops' argument validation (csrc/bcos_tapconv_dispatch.hip: validate) rejects (include/bcos_hip.h): nothing is asked of them."""
     if r.cgroup and (e.norm or e.max_out or e.absmax or e.norm_out or e.bias or e.ch_scale or e.ch_shift or (e.flags & EPI_MUL_FROM_ACT)
                      or e.rowadd or e.addend_sub > 1 or e.row_scale or e.misalign):
         return True                                          # out_cgroup launches are plain gradient launches

@@ -87,6 +87,13 @@ def test_build_tracks_every_header():
     assert present <= {os.path.realpath(str(h)) for h in lib.HEADERS}, present
 
 
+def test_build_compiles_every_unit():
+    """A unit dropped into csrc/ and forgotten in lib.SOURCES fails here, not at link time: the build's units are exactly csrc/*.hip."""
+    from bcos_hip import lib
+    assert len(lib.SOURCES) == len(set(lib.SOURCES))
+    assert set(lib.SOURCES) == {f for f in os.listdir(lib.CSRC) if f.endswith(".hip")}
+
+
 def test_abi_argument_validation_without_gpu(hip_lib):
     """Bad arguments are rejected before any HIP call, with an errno-style code and a message."""
     from bcos_hip import lib
