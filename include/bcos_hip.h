@@ -863,6 +863,38 @@ int bcos_channel_axpby(const float* a, const float* sa, const float* b, const fl
 
 /* -- transformer pieces (bcos_vit.hip) ---------------------------------------------------- */
 
+/* Accuracy, per element, of the LayerNorm / GroupNorm / GELU / un-patchify entry points of this section and of their training-mode
+ * gradients further down (tests/token_cases.py, tests/test_token_kernels_gpu.py).  Against the same expressions in fp64 from the fp32
+ * inputs (eps as the float passed; the gradients from the fp32 rstd they are GIVEN, not from an fp64 recomputation), with u = 2^-24,
+ * a LayerNorm row / GroupNorm (image, group) of n values, A = max |x| over it, sd = sqrt(var + eps), xh = x_hat and
+ * E(xh, q) = |xh| + q (1 + |xh|) -- `x - mean` is exact only to u A, which is u A / sd in x_hat and a relative u A / sd in sd:
+ *     |y - y64|        <= 12.0 u ( |weight| E(xh, A / sd) + |y64| )
+ *     |rstd sd - 1|    <=  5.6 u ( 1 + A / sd )
+ *     |zsumsq - z64|   <=  6.0 u ( z64 + 2 sum_c |y64| (the bracket of the first line) )
+ *     detached gradients, h = gy weight rstd:
+ *     |out - out64|    <=  7.6 u ( |h| + mean |h| + |addend| + |out64| ),     out2: that form times |mul2|, plus |out2_64|
+ *     full gradients, h = gy weight, rs = rstd, xh = (x - mean) rs, E = E(xh, A rs):
+ *     |gx - gx64|      <=  8.4 u ( rs (|h| + mean |h|) + rs (E mean |h xh| + |xh| mean (|h| E)) + |addend| + |gx64| )
+ *     |xhat_out - xh|  <= 12.0 u ( E + |xh| )
+ * No term takes credit for cancellation: a row whose mean is 1000 x its spread, or a constant row (sd = sqrt(eps)), is held to the
+ * A / sd term and no closer -- a constant row of 1000s may come out as 0.02.  x_absmax is bit-equal to max |x| of the row;
+ * y_absmax / out2_absmax are bit-equal to the row maximum of the y / out2 the same launch wrote.
+ * GELU, with Phi = 0.5 erfc(-x / sqrt 2), phi the normal density, z = |x| / sqrt 2, t = 1 / (1 + 0.3275911 z), the condition number
+ * c(t) = sum_k |a_k| t^k / sum_k a_k t^k of the alternating polynomial of Abramowitz-Stegun 7.1.26 (1.7 .. 4.5) and
+ * G = (c(t) + 2 z^2) min(Phi, 1 - Phi) + Phi:
+ *     |gate - Phi|     <= 0.75e-7 + 7.2 u G           (0.75e-7: half the 1.5e-7 that 7.1.26 states for erf -- an ABSOLUTE error: below
+ *                                                      x ~ -5.3 the gate itself is smaller)
+ *     |y - x Phi|      <= |x| (that bound) + u |x Phi|
+ *     |gx - gx64|      <= |gy| ( 0.75e-7 + 10.0 u ( G + |x| phi (1 + x^2) ) ) + u |gx64|           (bcos_gelu_bwd)
+ * bcos_gelu_gate may be called in place (y = x) with the same bits.  bcos_add_rows_bcast is exact (x + pe[i % period] in fp32).
+ * bcos_finalize_explanation_patches:  |W - W64| <= 4.4 u |W64|,  |contrib - c64| <= 19.6 u sum_ch |x6 W64|  (x6 = [x, 1 - x] under
+ * add_inverse); channels c >= 6 of a gp record are never used (they are loaded on the 16-byte path: Cpad = 8, gp 16-byte aligned).
+ * Each constant is 4 x the worst use of its form by a plain fp32 evaluation of the same expression over the test's case tables
+ * (LayerNorm widths 1 .. 1000 on both kernel forms and every NV of the statistics kernel, rows that leave wavefront groups partly
+ * empty, second passes of every grid-stride loop, misaligned views, offset / constant / outlier rows and rows decades apart; groups
+ * of 1 .. 18816 values; GELU over [-14, 14]; rectangular images and patch sizes 1 .. 16).  None of these kernels has atomics:
+ * a call repeated gives the same bits, and no output depends on which optional outputs were requested. */
+
 /* LayerNorm over the last dimension D of x [rows, D] (weight / bias may be NULL); rstd_out (NULL or [rows]) keeps
  * 1/sqrt(var+eps) for the backward.  Forward of DetachableLayerNorm (bcos/modules/norms/centered_norms.py:197-224;
  * the value does not depend on explanation mode).  y_absmax (NULL or [rows], ABI v5): the fp32 bit pattern of max_c |y[r,c]|,
@@ -934,6 +966,8 @@ int bcos_attention_bwd_v(const float* qkv, const float* stats, const float* gout
                          int H, int Dh, float scale, void* stream);
 
 /* -- training-mode backward of the token path (nothing detached; SURVEY.md section 8(f) N4 for the ViT family) ---------- */
+/* (Accuracy, per element, of bcos_layernorm_bwd / _bwd_add, bcos_groupnorm_bwd and bcos_gelu_bwd: the `full gradients`, `xhat_out` and
+ * `gx` lines of the paragraph at the head of the transformer section.) */
 /* LayerNorm over the last dimension (centered_norms.py:187-245 outside explanation mode = F.layer_norm's gradient):
  * gx = rstd (h - mean(h) - x_hat mean(h x_hat)), h = gy * weight, x_hat = (x - mean) rstd; xhat_out (NULL or [rows, D])
  * receives x_hat for the weight gradient sum_rows gy x_hat (bcos_colsum). */
@@ -957,7 +991,8 @@ int bcos_attention_bwd(const float* qkv, const float* stats, const float* out, c
                        int B, int T, int H, int Dh, float scale, void* stream);
 
 /* End of the ViT explanation pass: gp [N, H/p, W/p, p, p, Cpad] (input gradient of the patch embedding, one row per
- * patch in the "(p1 p2 c)" order of vit.py:291) -> W(x) [N,6,H,W] (/ std) and contribution map [N,H,W]. */
+ * patch in the "(p1 p2 c)" order of vit.py:291) -> W(x) [N,6,H,W] (/ std) and contribution map [N,H,W].  Either output may be
+ * NULL, H and W need not be equal; accuracy per element: the paragraph at the head of the transformer section. */
 int bcos_finalize_explanation_patches(const float* gp, const float* x, const float* std6, float* weights_out,
                                       float* contrib_out, int N, int Cx, int H, int W, int patch, int Cpad,
                                       int add_inverse, void* stream);
