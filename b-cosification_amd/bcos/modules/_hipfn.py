@@ -137,6 +137,7 @@ class WeightCache:
         self._key = None
         self._fwd = None
         self._dgrad = {}
+        self._dw7 = None
         self._transient = False
 
     def _sync(self, w, w_eff):
@@ -144,7 +145,7 @@ class WeightCache:
         # set_scale / toggle_weight_norm change w_eff while the parameter stays the same (bcosconv2d.py:26-41)
         key = (w.data_ptr(), w._version, tuple(w.shape), str(w.device), w_eff.data_ptr(), w_eff._version)
         if key != self._key:
-            self._key, self._fwd, self._dgrad, self._transient = key, None, {}, False
+            self._key, self._fwd, self._dgrad, self._dw7, self._transient = key, None, {}, None, False
 
     def fwd(self, w_eff, src):
         """w_eff: effective OIHW (or [O,I]) weight actually used (after unit-norm projection if any)."""
@@ -162,6 +163,15 @@ class WeightCache:
         elif not (torch.is_grad_enabled() and src.requires_grad):
             ops.publish_pending()
         return self._fwd
+
+    def dw7(self, w_eff, src):
+        """tap-major image [7,7,C] of a depthwise 7x7 filter bank (ops.dwconv7_weight_image), one per weight version"""
+        self._sync(src, w_eff)
+        if self._dw7 is None:
+            self._dw7 = ops.dwconv7_weight_image(w_eff)
+        elif not (torch.is_grad_enabled() and src.requires_grad):
+            ops.publish_pending()
+        return self._dw7
 
     def dgrad(self, w_eff, src, stride, padding, dilation, groups):
         self._sync(src, w_eff)
@@ -398,6 +408,62 @@ class BcosConv2dFn(Function):
         return gx_cl, gw, gb, None, gbp
 
 
+def is_depthwise7(in_channels, out_channels, kernel_size, stride, padding, dilation, groups, max_out=1) -> bool:
+    """The one grouped geometry with a kernel of its own (csrc/bcos_dwconv.hip): a depthwise 7x7 layer, stride 1, padding 3, no
+    dilation, no MaxOut -- the first layer of a ConvNeXt block.  Every other grouped geometry stays on the grouped route of
+    bcos_tapconv (BcosConv2dFn), with its requirement in_channels / groups % 4 == 0."""
+    return bool(groups > 1 and groups == in_channels == out_channels and max_out == 1 and _pair(kernel_size) == (7, 7)
+                and _pair(stride) == (1, 1) and _pair(padding) == (3, 3) and _pair(dilation) == (1, 1))
+
+
+def conv_is_depthwise7(lin, max_out=1) -> bool:
+    return isinstance(lin.padding, tuple) and is_depthwise7(lin.in_channels, lin.out_channels // max_out, lin.kernel_size, lin.stride,
+                                                             lin.padding, lin.dilation, lin.groups, max_out)
+
+
+DEPTHWISE_NO_TRAINING = ("depthwise B-cos layers do not train yet: the depthwise 7x7 kernel has the forward pass and the explanation-mode "
+                         "input gradient only (no weight gradient, no gradient through the B-cos scale); wrap the call in "
+                         "model.explanation_mode() or torch.no_grad()")
+
+
+class BcosDwConv7Fn(Function):
+    """Depthwise 7x7 B-cos convolution (is_depthwise7): one launch forward (bcos_dwconv7_fwd), one launch for the explanation-mode
+    input gradient (bcos_dwconv7_bwd on the kept scale).  cfg keys: b, detach.  The forward runs in any mode; a backward that
+    would need the scale's derivative or a weight / bias gradient raises DEPTHWISE_NO_TRAINING."""
+
+    @staticmethod
+    def forward(ctx, x, w_eff, bias, cfg, b_param=None):
+        require_hip(x, "BcosConv2d (depthwise)")
+        if bias is not None:
+            raise BcosHipError("BcosConv2d (depthwise 7x7): a bias is not implemented by the depthwise kernel")
+        if x.shape[1] % 4:
+            raise BcosHipError(f"BcosConv2d (depthwise 7x7): channels % 4 == 0 is required (got {x.shape[1]})")
+        b = float(cfg["b"])
+        N, Cc, H, W = x.shape
+        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        need_bp = b_param is not None and ctx.needs_input_grad[4] and _b_gradient_applies(cfg, b)
+        ctx.refuse = bool(need_w or need_bp or (need_x and not cfg["detach"] and b != 1.0))
+        wimg = cfg["cache"].dw7(w_eff, cfg["w_src"])
+        y_cl, y = empty_cl(N, Cc, H, W, x.device)
+        _, scale, _ = ops.dwconv7_fwd(to_nhwc(x), wimg, b=b, want_scale=bool(need_x and not ctx.refuse and b != 1.0), out=y)
+        ctx.wimg = wimg
+        if scale is not None:
+            ctx.save_for_backward(scale)
+        return y_cl
+
+    @staticmethod
+    def backward(ctx, gy):
+        if ctx.refuse:
+            raise BcosHipError(DEPTHWISE_NO_TRAINING)
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None
+        scale = ctx.saved_tensors[0] if ctx.saved_tensors else None
+        N, Cc, H, W = gy.shape
+        gx_cl, gx = empty_cl(N, Cc, H, W, gy.device)
+        ops.dwconv7_bwd(to_nhwc(gy), ctx.wimg, mul=scale, out=gx)
+        return gx_cl, None, None, None, None
+
+
 class BcosLinearFn(Function):
     """y = bcos_linear(x) over the last dimension.  cfg keys: b, max_out, detach, cache, w_src."""
 
@@ -504,6 +570,8 @@ def plain_conv2d(x, w_eff, bias, stride, padding, dilation, groups, cache, w_src
     """Un-scaled convolution on the same kernel (NormedConv2d called on its own)."""
     cfg = dict(stride=stride, padding=padding, dilation=dilation, groups=groups, b=1, max_out=1, detach=True,
                cache=cache, w_src=w_src)
+    if is_depthwise7(x.shape[1], w_eff.shape[0], tuple(w_eff.shape[2:]), stride, padding, dilation, groups):
+        return BcosDwConv7Fn.apply(x, w_eff, bias, cfg)
     return BcosConv2dFn.apply(x, w_eff, bias, cfg)
 
 

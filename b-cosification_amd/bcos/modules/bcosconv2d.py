@@ -155,6 +155,10 @@ class BcosConv2d(DetachableModule):
         cfg = dict(stride=tuple(lin.stride), padding=tuple(lin.padding), dilation=tuple(lin.dilation),
                    groups=lin.groups, b=self._b_value(), max_out=self.max_out, detach=self.detach,
                    cache=self._wcache, w_src=lin.weight)
+        if _hipfn.conv_is_depthwise7(lin, self.max_out):
+            # depthwise 7x7 (ConvNeXt): a vector kernel of its own, forward and explanation-mode input gradient
+            w, bias = self._effective_weight_and_bias()
+            return _hipfn.BcosDwConv7Fn.apply(in_tensor, w, bias, cfg, _hipfn.learnable_b(self))
         if isinstance(lin, NormedConv2d) and lin.use_weight_norm and _hipfn.folds_projection(lin, self.detach):
             # training step of a native layer: the unit-norm projection is folded into the contraction (one forward launch)
             return _hipfn.FoldedUnitNormFn.apply(in_tensor, lin.weight, lin.scale, cfg, _hipfn.learnable_b(self), _hipfn.BcosConv2dFn)
@@ -166,6 +170,10 @@ class BcosConv2d(DetachableModule):
         with a zero filter bank, writing only the norms."""
         lin = self.linear
         _hipfn.require_hip(in_tensor, "calc_patch_norms")
+        if _hipfn.conv_is_depthwise7(lin, self.max_out):      # one norm per channel: the depthwise kernel's norm output
+            w, _ = self._effective_weight_and_bias()
+            _, _, norm = ops.dwconv7_fwd(_hipfn.to_nhwc(in_tensor), ops.dwconv7_weight_image(w.detach()), b=self._b_value(), want_norm=True)
+            return _hipfn.from_nhwc(norm)
         x = _hipfn.to_nhwc(in_tensor)
         N, H, W, Cin = x.shape
         kh, kw = lin.kernel_size

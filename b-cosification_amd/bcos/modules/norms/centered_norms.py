@@ -17,7 +17,7 @@ from bcos_hip import ops
 from bcos.modules import _hipfn
 from bcos.modules.common import DetachableModule
 
-__all__ = ["DetachableLayerNorm", "DetachableGroupNorm2d", "DetachableGNInstanceNorm2d", "DetachableGNLayerNorm2d"]
+__all__ = ["DetachableLayerNorm", "DetachablePositionNorm2d", "DetachableGroupNorm2d", "DetachableGNInstanceNorm2d", "DetachableGNLayerNorm2d"]
 
 
 class _LayerNormFn(Function):
@@ -82,6 +82,23 @@ class DetachableLayerNorm(nn.LayerNorm, DetachableModule):
             if standard_module.bias is not None:
                 new.bias.data = standard_module.bias.data
         return new
+
+
+class DetachablePositionNorm2d(nn.LayerNorm, DetachableModule):
+    """LayerNorm over the channels of every position of a [N,C,H,W] tensor (reference :251-298; the norm of the B-cos ConvNeXts):
+    on the NHWC image that is a LayerNorm over rows, so forward and gradients are those of _LayerNormFn -- explanation mode keeps
+    the variance constant and the mean differentiable (:283-298), otherwise F.layer_norm's gradient (:277-281)."""
+
+    def __init__(self, features: int, eps: float = 1e-5, affine: bool = True, device=None, dtype=None) -> None:
+        assert isinstance(features, int), f"Provide #features as an int not {type(features)=}"
+        DetachableModule.__init__(self)
+        super().__init__(normalized_shape=features, eps=eps, elementwise_affine=affine, device=device, dtype=dtype)
+        self.features = features
+
+    def forward(self, x: Tensor) -> Tensor:
+        assert x.dim() == 4, f"input should be 4D not {x.dim()}D"
+        y = _LayerNormFn.apply(_hipfn.to_nhwc(x), self.weight, self.bias, self.eps, self.detach)
+        return _hipfn.from_nhwc(y)
 
 
 class _GroupNormFn(Function):

@@ -1201,6 +1201,55 @@ def mul(a, b, out=None):
     return out
 
 
+# ---- depthwise 7x7 B-cos convolution (csrc/bcos_dwconv.hip) ---------------------------------------------------------------
+def dwconv7_weight_image(w_eff: torch.Tensor) -> torch.Tensor:
+    """Tap-major image [7,7,C] of a depthwise filter bank [C,1,7,7] (the effective, unit-normed weight), cached on the weight tensor
+    like the other weight images: keyed by data pointer and version, published once for launches on any stream."""
+    if w_eff.dim() != 4 or tuple(w_eff.shape[1:]) != (1, 7, 7):
+        raise BcosHipError(f"dwconv7: expected a depthwise filter bank [C,1,7,7], got {tuple(w_eff.shape)}")
+    cached = getattr(w_eff, "_bcos_dw7", None)
+    key = (w_eff.data_ptr(), w_eff._version)
+    if cached is None or cached[0] != key:
+        cached = (key, w_eff.detach()[:, 0].permute(1, 2, 0).contiguous())
+        w_eff._bcos_dw7 = cached
+        publish_cached(cached[1])
+    elif _PENDING:
+        publish_pending()
+    return cached[1]
+
+
+def _dw_shape(t, w, who):
+    if t.dim() != 4 or w.dim() != 3 or tuple(w.shape) != (7, 7, t.shape[3]):
+        raise BcosHipError(f"{who}: expected an NHWC tensor [N,H,W,C] and a filter image [7,7,C], got {tuple(t.shape)} and {tuple(w.shape)}")
+    return t.shape
+
+
+def dwconv7_fwd(x_nhwc, w, b=2.0, want_scale=False, want_norm=False, out=None):
+    """Depthwise 7x7 B-cos convolution, stride 1, padding 3 (include/bcos_hip.h: bcos_dwconv7_fwd): (y, scale or None, norm or None),
+    all [N,H,W,C].  `w` is the tap-major image [7,7,C] of the effective filters (dwconv7_weight_image)."""
+    lib = _l.load()
+    N, H, W, Cc = _dw_shape(x_nhwc, w, "dwconv7_fwd")
+    y = out if out is not None else torch.empty_like(x_nhwc)
+    scale = torch.empty_like(x_nhwc) if want_scale else None
+    norm = torch.empty_like(x_nhwc) if want_norm else None
+    _l.check(lib.bcos_dwconv7_fwd(_dev(x_nhwc, "x"), _dev(w, "w"), _dev(y, "y"), _dev(scale, "scale"), _dev(norm, "norm"),
+                                  N, H, W, Cc, float(b), _stream()), "bcos_dwconv7_fwd")
+    return y, scale, norm
+
+
+def dwconv7_bwd(gy, w, mul=None, addend=None, out=None):
+    """Explanation-mode input gradient of dwconv7_fwd: addend + conv_transpose(mul * gy, w) per channel (bcos_dwconv7_bwd)."""
+    lib = _l.load()
+    N, H, W, Cc = _dw_shape(gy, w, "dwconv7_bwd")
+    for t, name in ((mul, "mul"), (addend, "addend")):
+        if t is not None and t.shape != gy.shape:
+            raise BcosHipError(f"dwconv7_bwd: {name} has shape {tuple(t.shape)}, gy {tuple(gy.shape)}")
+    gx = out if out is not None else torch.empty_like(gy)
+    _l.check(lib.bcos_dwconv7_bwd(_dev(gy, "gy"), _dev(w, "w"), _dev(mul, "mul"), _dev(addend, "addend"), _dev(gx, "gx"),
+                                  N, H, W, Cc, _stream()), "bcos_dwconv7_bwd")
+    return gx
+
+
 def maxout_expand(gy2d, t2d, max_out):
     """glin[r, c] = gy[r, c // M] * t[r, c]: backward of the fused MaxOut (include/bcos_hip.h: bcos_maxout_expand)."""
     lib = _l.load()

@@ -128,8 +128,9 @@ class FusedPlan:
 
     def __init__(self, net, subbatch_streams=_SUBBATCH_STREAMS):
         self.net = net
-        norm = net.bcosifynormalize
-        self._mean, self._std = tuple(norm.mean), tuple(norm.std)
+        norm = getattr(net, "bcosifynormalize", None)
+        # (a native B-cos network takes the 6-channel image as it is: mean 0 / std 1 leave every value's bits alone)
+        self._mean, self._std = (tuple(norm.mean), tuple(norm.std)) if norm is not None else ((0.0,) * 6, (1.0,) * 6)
         self._dev_consts = {}
         ll = net.logit_layer
         self.logit_bias = ll.logit_bias if ll is not None else None

@@ -132,6 +132,34 @@ def build_bcosified_densenet(growth: int = 32, block_config=(6, 12, 24, 16), ini
     return net.eval()
 
 
+def seed_convnext(net: nn.Module, seed: int = 0):
+    """Every parameter of a B-cos ConvNeXt redrawn from one generator, in state-dict order, so that two implementations of the same
+    topology (this package's, the reference's in the golden generator) hold identical weights whatever their constructors drew:
+    filters ~ N(0, 0.02^2) (unit-normed by the layer anyway), `layer_scale` ~ U(0.25, 1) -- the constructor's default of 1e-6 would make
+    every block numerically invisible and every test blind to it --, norm weights ~ U(0.5, 1.5)."""
+    gen = torch.Generator().manual_seed(seed)
+    with torch.no_grad():
+        for name, p in net.named_parameters():
+            if name.endswith("layer_scale"):
+                p.copy_(torch.rand(p.shape, generator=gen) * 0.75 + 0.25)
+            elif p.dim() == 1:
+                p.copy_(torch.rand(p.shape, generator=gen) + 0.5)
+            else:
+                p.copy_(torch.randn(p.shape, generator=gen) * 0.02)
+    return net
+
+
+def build_bcos_convnext(block_setting, num_classes: int = 1000, seed: int = 0, convnext_module=None):
+    """A seeded native B-cos ConvNeXt (bcos/models/convnext.py) in eval mode.  `block_setting`: (input channels, output channels or None,
+    blocks) per stage.  `convnext_module` lets the golden generator pass the reference's own bcos.models.convnext."""
+    if convnext_module is None:
+        from bcos.models import convnext as convnext_module
+    stages = [convnext_module.CNBlockConfig(*s) for s in block_setting]
+    torch.manual_seed(seed)
+    net = convnext_module.BcosConvNeXt(stages, num_classes=num_classes)
+    return seed_convnext(net, seed).eval()
+
+
 def synthetic_images(n: int, seed: int = 123, size: int = 224, smooth: bool = True) -> torch.Tensor:
     """[n,6,size,size] AddInverse-encoded images in [0,1].  `smooth`: bilinearly upsampled 14x14 noise plus a
     per-image colour offset (pure pixel noise makes every image predict the same class)."""

@@ -63,11 +63,6 @@ __global__ __launch_bounds__(TPB) void mul_kernel(const float* __restrict__ a, c
     for (int64_t i = n4 * 4 + (int64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += stride) out[i] = a[i] * b[i];
 }
 
-__device__ inline float bcos_scale_of(float lin, float nrm, float b) {
-    if (b == 2.0f) return fabsf(lin) / nrm;
-    return powf(fabsf(lin / nrm) + 1e-6f, b - 1.0f);
-}
-
 // ---- MaxOut + scaling, general path ----------------------------------------------------------
 __global__ __launch_bounds__(TPB) void maxout_scale_kernel(const float* __restrict__ lin,
                                                            const float* __restrict__ norm, float* __restrict__ y,

@@ -65,6 +65,13 @@ inline hipError_t bcos_ensure_dynamic_lds(const void* fn, size_t bytes, std::ato
 // |error| <= 1.5e-7 -- on v_rcp_f32 / v_exp_f32: ~14 vector instructions where the library erff takes ~45 (the 192 -> 768 GELU launches
 // of the ViT plan were 64 us of 257 slower than the same contraction without it).  Absolute error of the gate <= 1e-7.
 #ifdef __HIPCC__
+// B-cos multiplier |cos|^(B-1) of one output from its linear response and its patch norm (bcosconv2d.py:176-194), one definition for the
+// kernels that evaluate it per element outside a contraction's tile epilogue (MaxOut + scaling, the depthwise convolution): IEEE division
+__device__ inline float bcos_scale_of(float lin, float nrm, float b) {
+    if (b == 2.0f) return fabsf(lin) / nrm;
+    return powf(fabsf(lin / nrm) + 1e-6f, b - 1.0f);
+}
+
 __device__ __forceinline__ float bcos_gelu_gate(float x) {
     const float z = fabsf(x) * 0.70710678118654752f;
     const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, z, 1.0f));

@@ -1351,6 +1351,29 @@ int bcos_siglip_loss(const float* s, const float* t, const float* scale, const f
 /* floats = (L N + M) (D + 1) + 2 L N M + N M + 3 N.  BCOS_E_INVAL: floats NULL or sizes that bcos_siglip_loss refuses. */
 int bcos_siglip_loss_ws_floats(int L, int N, int M, int D, int64_t* floats);
 
+/* -- depthwise 7x7 B-cos convolution (csrc/bcos_dwconv.hip) ------------------------------------------------------------
+ * The first layer of a ConvNeXt block (bcos/models/convnext.py: BcosConv2d(dim, dim, kernel_size=7, padding=3, groups=dim)): one
+ * filter per channel, so there is nothing for the matrix pipe to contract -- a vector kernel, lanes along channels.
+ *   x [N,H,W,C] NHWC fp32,  w [7,7,C] tap-major, channel-contiguous: the EFFECTIVE (already unit-normed) filter bank,
+ *   stride 1, zero padding 3, dilation 1, C % 4 == 0.
+ * Per output element (p, c), over the taps t = (r, s) in row-major ascending order, r outer (taps outside the image read x = 0, which
+ * leaves both chains' bits as they were):
+ *   lin = fma(w[t,c], x[p+t-3,c], lin)      ss = fma(x[p+t-3,c], x[p+t-3,c], ss)        (both start at 0)
+ *   norm = sqrt(ss + 1e-6): with groups = C every channel has its own patch norm (bcosconv2d.py:196-231)
+ *   scale = |lin| / norm (B = 2),  (|lin / norm| + 1e-6)^(B-1) otherwise;   y = scale * lin;   B = 1: y = lin
+ * IEEE division and square root.  scale_out / norm_out ([N,H,W,C] each) may be NULL; with B = 1 scale_out must be NULL.
+ * bcos_dwconv7_bwd is the explanation-mode input gradient (the scale is a constant):
+ *   gx[p,c] = addend[p,c] + sum_t w[t,c] (mul gy)[p-t+3,c]
+ * one FMA chain from 0 over the SOURCE pixels p-t+3 in row-major ascending order (t descending), then one addition of addend; mul
+ * (the kept forward scale) and addend (the residual stream's gradient) may be NULL.  gx may alias addend, not gy or mul.
+ * One thread owns an output element: no atomics, and the bits depend neither on N, nor on the image's position in the batch, nor on
+ * the launch shape.  BCOS_E_INVAL, before any HIP call: a NULL x / w / y (gy / w / gx), a size <= 0, C % 4 != 0, a pointer that
+ * is not 16-byte aligned, scale_out with B = 1, or more than 2^31 - 1 workgroups. */
+int bcos_dwconv7_fwd(const float* x, const float* w, float* y, float* scale_out, float* norm_out, int N, int H, int W, int C, float b,
+                     void* stream);
+int bcos_dwconv7_bwd(const float* gy, const float* w, const float* mul, const float* addend, float* gx, int N, int H, int W, int C,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif
