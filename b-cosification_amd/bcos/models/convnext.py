@@ -7,6 +7,8 @@ the classes) runs BEFORE the global average pool (:202-208), then the LogitLayer
 A block (:45-65) is: depthwise 7x7 B-cos conv -> position norm -> 1x1 B-cos conv to 4 dim -> 1x1 B-cos conv back to dim (no GELU: the
 B-cos transform is the non-linearity), times `layer_scale`, stochastic depth, plus the block input.  The depthwise layer is the one
 piece with a kernel of its own (csrc/bcos_dwconv.hip, routed by BcosConv2d); the norms are DetachablePositionNorm2d without bias.
+Every block opts its depthwise layer in to the training-mode gradients (csrc/bcos_dwconv_train.hip), so `net.train(); net(x);
+loss.backward()` trains a BcosConvNeXt per layer like the reference; a bare depthwise BcosConv2d still refuses them.
 
 torchvision is not part of this package's requirements, so `StochasticDepth` ("row" mode, torchvision.ops.StochasticDepth) is restated
 here: the identity in eval mode or at p = 0.
@@ -20,6 +22,7 @@ from torch import Tensor, nn
 
 from bcos.common import BcosUtilMixin
 from bcos.modules import BcosConv2d, LogitLayer, norms
+from bcos.modules._hipfn import conv_is_depthwise7
 
 __all__ = ["BcosConvNeXt", "convnext_atto", "convnext_tiny", "convnext_small", "convnext_base", "convnext_large", "CNBlock",
            "CNBlockConfig", "StochasticDepth"]
@@ -68,6 +71,9 @@ class CNBlock(nn.Module):
             conv_layer(in_channels=dim, out_channels=4 * dim, kernel_size=1, bias=False),
             conv_layer(in_channels=4 * dim, out_channels=dim, kernel_size=1, bias=False),
         )
+        dw = self.block[0]
+        if isinstance(dw, BcosConv2d) and conv_is_depthwise7(dw.linear, dw.max_out):
+            dw.enable_depthwise_training()          # the training-mode gradients of csrc/bcos_dwconv_train.hip
         self.layer_scale = nn.Parameter(torch.ones(dim, 1, 1) * layer_scale)
         self.stochastic_depth = StochasticDepth(stochastic_depth_prob, "row")
 

@@ -11,6 +11,8 @@ Backward:
     (bcos_maxout_scatter); a learnable exponent (`b` an nn.Parameter, trainer.py:451-463) receives
     sum g y ln(|cos| + 1e-6) times d B_eff / d b; native layers differentiate through their unit-norm projection (UnitNormFn).
 Grouped MaxOut layers train per group too; only units that would straddle two groups (out_channels % groups != 0) raise.
+Depthwise 7x7 layers (ConvNeXt) have kernels of their own: BcosDwConv7Fn (forward, explanation-mode input gradient; refuses training
+gradients) and, for layers that opted in, BcosDwConv7TrainFn (csrc/bcos_dwconv_train.hip: scale differentiated, filter gradient).
 """
 import torch
 import torch.nn.functional as F
@@ -423,7 +425,8 @@ def conv_is_depthwise7(lin, max_out=1) -> bool:
 
 DEPTHWISE_NO_TRAINING = ("depthwise B-cos layers do not train yet: the depthwise 7x7 kernel has the forward pass and the explanation-mode "
                          "input gradient only (no weight gradient, no gradient through the B-cos scale); wrap the call in "
-                         "model.explanation_mode() or torch.no_grad()")
+                         "model.explanation_mode() or torch.no_grad(), or opt the layer in to the training-mode kernels with "
+                         "BcosConv2d.enable_depthwise_training() (every CNBlock of bcos.models.convnext does)")
 
 
 class BcosDwConv7Fn(Function):
@@ -462,6 +465,63 @@ class BcosDwConv7Fn(Function):
         gx_cl, gx = empty_cl(N, Cc, H, W, gy.device)
         ops.dwconv7_bwd(to_nhwc(gy), ctx.wimg, mul=scale, out=gx)
         return gx_cl, None, None, None, None
+
+
+class BcosDwConv7TrainFn(Function):
+    """Depthwise 7x7 B-cos convolution of a layer that opted in to training (BcosConv2d.enable_depthwise_training; every CNBlock does):
+    the forward launch of BcosDwConv7Fn, and a backward with the scale differentiated (bcosconv2d.py:176-194 without .detach()):
+      gx = bcos_dwconv7_train_bwd(g; x, y, scale, norm)          one launch
+      gw = bcos_dwconv7_wgrad(g, x, mul = scale, gain = 2)       the gradient of the EFFECTIVE filters, [7,7,C] -> [C,1,7,7]; the raw
+                                                                 weight's comes from UnitNormFn, which put w_eff into the graph
+    In explanation mode (or with B = 1) the scale is a constant: gx is BcosDwConv7Fn's launch, bit for bit, and a wanted weight gradient
+    is bcos_dwconv7_wgrad(g, x, mul = scale, gain = 1).  A bias and a learnable B still raise."""
+
+    @staticmethod
+    def forward(ctx, x, w_eff, bias, cfg, b_param=None):
+        require_hip(x, "BcosConv2d (depthwise)")
+        if bias is not None:
+            raise BcosHipError("BcosConv2d (depthwise 7x7): a bias is not implemented by the depthwise kernel")
+        if x.shape[1] % 4:
+            raise BcosHipError(f"BcosConv2d (depthwise 7x7): channels % 4 == 0 is required (got {x.shape[1]})")
+        b = float(cfg["b"])
+        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if b_param is not None and ctx.needs_input_grad[4] and _b_gradient_applies(cfg, b):
+            raise BcosHipError("BcosConv2d (depthwise 7x7): a learnable B is not differentiated by the depthwise kernels")
+        train = bool((need_x or need_w) and not cfg["detach"] and b != 1.0)          # the scale is differentiated
+        if train and b != 2.0:
+            raise BcosHipError(f"BcosConv2d (depthwise 7x7): training gradients exist for B = 2 and B = 1 only (got B = {b:g})")
+        N, Cc, H, W = x.shape
+        if need_w:       # a weight under autograd changes with the step: its image lives for this one, on this stream
+            wimg = w_eff.detach()[:, 0].permute(1, 2, 0).contiguous()
+        else:
+            wimg = cfg["cache"].dw7(w_eff, cfg["w_src"])
+        xh = to_nhwc(x)
+        y_cl, y = empty_cl(N, Cc, H, W, x.device)
+        _, scale, norm = ops.dwconv7_fwd(xh, wimg, b=b, want_scale=bool((need_x or need_w) and b != 1.0), want_norm=train, out=y)
+        ctx.wimg, ctx.b, ctx.train = wimg, b, train
+        keep = (xh if (train or need_w) else None, y_cl if train else None, scale, norm)
+        ctx.has = tuple(t is not None for t in keep)
+        ctx.save_for_backward(*(t for t in keep if t is not None))
+        return y_cl
+
+    @staticmethod
+    def backward(ctx, gy):
+        saved = list(ctx.saved_tensors)
+        xh, y_cl, scale, norm = (saved.pop(0) if h else None for h in ctx.has)
+        y = to_nhwc(y_cl) if y_cl is not None else None
+        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        N, Cc, H, W = gy.shape
+        g = to_nhwc(gy)
+        gx_cl = gw = None
+        if need_x:
+            gx_cl, gx = empty_cl(N, Cc, H, W, gy.device)
+            if ctx.train:
+                ops.dwconv7_train_bwd(g, xh, y, scale, norm, ctx.wimg, b=ctx.b, out=gx)
+            else:
+                ops.dwconv7_bwd(g, ctx.wimg, mul=scale, out=gx)
+        if need_w:
+            gw = ops.dwconv7_wgrad(g, xh, mul=scale, gain=2.0 if ctx.train else 1.0).permute(2, 0, 1).unsqueeze(1).contiguous()
+        return gx_cl, gw, None, None, None
 
 
 class BcosLinearFn(Function):

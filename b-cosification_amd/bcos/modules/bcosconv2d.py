@@ -145,6 +145,16 @@ class BcosConv2d(DetachableModule):
             object.__setattr__(self, "_b_cache", cached)
         return cached[1]
 
+    _depthwise_training = False        # (a class default: layers unpickled from before the flag behave as they did)
+
+    def enable_depthwise_training(self, on: bool = True):
+        """Route a depthwise 7x7 layer (_hipfn.conv_is_depthwise7) through BcosDwConv7TrainFn, whose backward differentiates the B-cos
+        scale and returns the filter gradient.  Off by default: a bare layer refuses training gradients (DEPTHWISE_NO_TRAINING)."""
+        if on and not _hipfn.conv_is_depthwise7(self.linear, self.max_out):
+            raise ValueError("enable_depthwise_training: not a depthwise 7x7 layer (stride 1, padding 3, groups = channels, no MaxOut)")
+        self._depthwise_training = bool(on)
+        return self
+
     def forward(self, in_tensor: Tensor) -> Tensor:
         return self.forward_impl(in_tensor)
 
@@ -156,9 +166,11 @@ class BcosConv2d(DetachableModule):
                    groups=lin.groups, b=self._b_value(), max_out=self.max_out, detach=self.detach,
                    cache=self._wcache, w_src=lin.weight)
         if _hipfn.conv_is_depthwise7(lin, self.max_out):
-            # depthwise 7x7 (ConvNeXt): a vector kernel of its own, forward and explanation-mode input gradient
+            # depthwise 7x7 (ConvNeXt): a vector kernel of its own, forward and explanation-mode input gradient; a layer that opted in
+            # (enable_depthwise_training) has the training-mode gradients too
             w, bias = self._effective_weight_and_bias()
-            return _hipfn.BcosDwConv7Fn.apply(in_tensor, w, bias, cfg, _hipfn.learnable_b(self))
+            fn = _hipfn.BcosDwConv7TrainFn if self._depthwise_training else _hipfn.BcosDwConv7Fn
+            return fn.apply(in_tensor, w, bias, cfg, _hipfn.learnable_b(self))
         if isinstance(lin, NormedConv2d) and lin.use_weight_norm and _hipfn.folds_projection(lin, self.detach):
             # training step of a native layer: the unit-norm projection is folded into the contraction (one forward launch)
             return _hipfn.FoldedUnitNormFn.apply(in_tensor, lin.weight, lin.scale, cfg, _hipfn.learnable_b(self), _hipfn.BcosConv2dFn)

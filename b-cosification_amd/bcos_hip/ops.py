@@ -1250,6 +1250,56 @@ def dwconv7_bwd(gy, w, mul=None, addend=None, out=None):
     return gx
 
 
+def dwconv7_train_bwd(gy, x, y, scale, norm, w, b=2.0, addend=None, out=None):
+    """Training-mode input gradient of dwconv7_fwd, the B-cos scale differentiated (include/bcos_hip.h: bcos_dwconv7_train_bwd), one
+    launch.  x, y, scale, norm: the forward's input and outputs (B = 1: not read, may be None)."""
+    lib = _l.load()
+    N, H, W, Cc = _dw_shape(gy, w, "dwconv7_train_bwd")
+    for t, name in ((x, "x"), (y, "y"), (scale, "scale"), (norm, "norm"), (addend, "addend")):
+        if t is not None and t.shape != gy.shape:
+            raise BcosHipError(f"dwconv7_train_bwd: {name} has shape {tuple(t.shape)}, gy {tuple(gy.shape)}")
+    gx = out if out is not None else torch.empty_like(gy)
+    _l.check(lib.bcos_dwconv7_train_bwd(_dev(gy, "gy"), _dev(x, "x"), _dev(y, "y"), _dev(scale, "scale"), _dev(norm, "norm"), _dev(w, "w"),
+                                        _dev(addend, "addend"), _dev(gx, "gx"), N, H, W, Cc, float(b), _stream()), "bcos_dwconv7_train_bwd")
+    return gx
+
+
+_DW7_WS = {}       # (device, stream) -> workspace of dwconv7_wgrad, grown on demand (written before it is read by every call)
+
+
+def dwconv7_wgrad_workspace(N, H, W, Cc) -> int:
+    """bytes of workspace bcos_dwconv7_wgrad needs at this shape (host arithmetic, no device)"""
+    need = int(_l.load().bcos_dwconv7_wgrad_workspace(int(N), int(H), int(W), int(Cc)))
+    if need < 0:
+        _l.check(need, "bcos_dwconv7_wgrad_workspace")
+    return need
+
+
+def dwconv7_wgrad(gy, x, mul=None, gain=1.0, out=None, workspace=None):
+    """Gradient [7,7,C] of the effective depthwise filter bank: sum over images and pixels of (gain * mul * gy) x at every tap
+    (include/bcos_hip.h: bcos_dwconv7_wgrad); two launches, no atomics, the same bits on every call.  The workspace is a cached buffer
+    per (device, stream) unless the caller brings one (`workspace`: an fp32 tensor of dwconv7_wgrad_workspace bytes or more)."""
+    lib = _l.load()
+    if gy.dim() != 4 or x.shape != gy.shape or (mul is not None and mul.shape != gy.shape):
+        raise BcosHipError(f"dwconv7_wgrad: expected NHWC tensors of one shape, got gy {tuple(gy.shape)}, x {tuple(x.shape)}"
+                           + (f", mul {tuple(mul.shape)}" if mul is not None else ""))
+    N, H, W, Cc = gy.shape
+    _dev(gy, "gy")
+    gw = out if out is not None else torch.empty((7, 7, Cc), device=gy.device, dtype=torch.float32)
+    _dw_shape(gy, gw, "dwconv7_wgrad")
+    st = _stream()
+    ws = workspace
+    if ws is None:
+        need = dwconv7_wgrad_workspace(N, H, W, Cc)
+        key = (gy.device.index, st.value)
+        ws = _DW7_WS.get(key)
+        if ws is None or ws.numel() * 4 < need:
+            ws = _DW7_WS[key] = torch.empty((max(need // 4, 1 << 16),), device=gy.device, dtype=torch.float32)
+    _l.check(lib.bcos_dwconv7_wgrad(_dev(gy, "gy"), _dev(mul, "mul"), float(gain), _dev(x, "x"), _dev(gw, "gw"), _dev(ws, "workspace"),
+                                    ws.numel() * 4, N, H, W, Cc, st), "bcos_dwconv7_wgrad")
+    return gw
+
+
 def maxout_expand(gy2d, t2d, max_out):
     """glin[r, c] = gy[r, c // M] * t[r, c]: backward of the fused MaxOut (include/bcos_hip.h: bcos_maxout_expand)."""
     lib = _l.load()

@@ -1374,6 +1374,42 @@ int bcos_dwconv7_fwd(const float* x, const float* w, float* y, float* scale_out,
 int bcos_dwconv7_bwd(const float* gy, const float* w, const float* mul, const float* addend, float* gx, int N, int H, int W, int C,
                      void* stream);
 
+/* -- training-mode gradients of the depthwise 7x7 B-cos convolution (csrc/bcos_dwconv_train.hip) ---------------------------
+ * The backward pass of bcos_dwconv7_fwd with the B-cos scale DIFFERENTIATED: what autograd derives from the reference's
+ * bcos/modules/bcosconv2d.py:176-194 (the `self.b == 2` branch :186-187 with `self.detach` off, the patch norm of :196-231) on a layer
+ * with groups = C.  B = 2 and B = 1 only; x, y, scale, norm are the forward's input and outputs, g = gy = dL/dy, all [N,H,W,C] fp32,
+ * w [7,7,C] the effective filter bank as in bcos_dwconv7_fwd.
+ *   glin = 2 (scale g)                    one rounded product, the doubling is exact     (dy/dlin = 2 |lin| / norm)
+ *   r    = -(g y) / (norm norm)           two rounded products, one IEEE division        (dy/dnorm = -y / norm, dnorm/dx_q = x_q / norm)
+ *   acc(q) = sum_t w_t glin(q - t + 3)    one FMA chain from 0 over the SOURCE pixels q - t + 3 in row-major ascending order
+ *   box(q) = sum_t r(q - t + 3)           one chain of additions from 0 in the same order (pixels outside the image add an exact zero)
+ *   gx(q)  = fma(x(q), box(q), acc(q)),   then one addition of addend(q) where addend != NULL
+ *   B = 1:  glin = g, gx = acc [+ addend]; x, y, scale, norm are not read and may be NULL.
+ * One launch; glin and r exist only in LDS.  One thread owns an output element: no atomics, the bits depend neither on N nor on the
+ * image's position in the batch.  gx may alias addend, nothing else.
+ * BCOS_E_INVAL, before any HIP call: B other than 1 or 2, a NULL gy / w / gx (B = 2: x / y / scale / norm too), a size <= 0,
+ * C % 4 != 0, a pointer (the optional ones included) that is not 16-byte aligned, more than 2^31 - 1 workgroups. */
+int bcos_dwconv7_train_bwd(const float* gy, const float* x, const float* y, const float* scale, const float* norm, const float* w,
+                           const float* addend, float* gx, int N, int H, int W, int C, float b, void* stream);
+/* Gradient of the EFFECTIVE (unit-norm) filter bank, gw [7,7,C] tap-major like w (the projection's own gradient stays
+ * bcos_weight_rownorm_bwd's; the reference gets both from autograd of F.conv2d in bcosconv2d.py:172):
+ *   glin = gain (mul gy) where mul != NULL (rounded as bcos_dwconv7_train_bwd rounds it), gain gy otherwise
+ *   gw(t, c) = sum_{n,p} glin_c(n, p) x_c(n, p + t - 3)                                   (x = 0 outside the image)
+ * Training passes mul = scale, gain = 2; mul = NULL, gain = 1 is the gradient with the scale held constant.
+ * Order of every sum, a function of (N, H, W, C) alone.  The images are cut into tiles of 6 x 8 pixels; the P = N ceil(H / 6) ceil(W / 8)
+ * (image, tile) pairs, image-major, tile rows before tile columns, are dealt in runs of L = ceil(P / 256) to G = ceil(P / L) workgroups
+ * per slice of 64 channels.  A workgroup keeps, per (tap, channel), two partial sums: part 0 over tile rows 0-2, part 1 over tile rows
+ * 3-5 of its pairs, each ONE FMA chain from 0 over pairs ascending, rows ascending, columns ascending (a pixel beyond the image adds an
+ * exact zero).  Partial (2 g + part) of workgroup g goes to ws [2 G][49][C]; a second launch adds the 2 G partials in ascending index,
+ * starting from partial 0.  No atomics: two calls on the same data give the same bits, whatever ws held before.
+ * BCOS_E_INVAL, before any HIP call: a NULL gy / x / gw / ws, a size <= 0, C % 4 != 0, a pointer (mul included) that is not 16-byte
+ * aligned, a gain that is not finite, ws_bytes < bcos_dwconv7_wgrad_workspace(N, H, W, C). */
+int bcos_dwconv7_wgrad(const float* gy, const float* mul, float gain, const float* x, float* gw, void* ws, int64_t ws_bytes, int N, int H,
+                       int W, int C, void* stream);
+/* bytes = 4 * 49 * C * 2 * G with G as above (at most 100352 C).  Host only, no device needed.  BCOS_E_INVAL (negative): a size <= 0,
+ * C % 4 != 0, or more than 2^31 - 1 bytes (C > 21396 at G = 256), which bcos_dwconv7_wgrad refuses as well. */
+int bcos_dwconv7_wgrad_workspace(int N, int H, int W, int C);
+
 #ifdef __cplusplus
 }
 #endif
