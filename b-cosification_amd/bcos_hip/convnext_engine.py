@@ -7,7 +7,8 @@ the base class's (bcos_hip/plan.py).  The network takes the 6-channel image as i
 
 Forward, per block -- four launches, no elementwise launch:
   1. bcos_dwconv7_fwd: the depthwise 7x7 B-cos convolution (its scale kept in an explanation pass);
-  2. bcos_layernorm_fwd over the rows of the NHWC image = the position norm (row rstd kept);
+  2. bcos_layernorm_fwd (bcos_layernorm_unc_fwd for the uncentered position norm) over the rows of the NHWC image = the position norm
+     (row rstd kept);
   3. the 1x1 expansion C -> 4C (its multiplier kept);
   4. the 1x1 projection 4C -> C with ch_scale = layer_scale and addend = the block input in its epilogue (its multiplier, layer_scale
      included, kept).
@@ -25,8 +26,8 @@ contractions keep the exact bf16x3 loop, as the ViT plan's do and as the module 
 DESIGN.md "ConvNeXt"): with row maxima the K = 96 -> 384 expansion of ConvNeXt-T's first stage takes the d_128x192 tile of the LDS-DMA
 loop, which returned wrong rows behind the last full 32768 rows at M > 32768 (batch 32 and up at 56^2), whichever kernel made the maxima.
 
-Scope: position-norm variants (DetachablePositionNorm2d, with or without bias), BcosConv2d with B = 2 fixed and max_out = 1, eval mode.
-Anything else -- the `_bnu` variants, a learnable or other B, MaxOut, a model in train() -- makes attach() raise BcosHipError; the module
+Scope: position-norm variants (DetachablePositionNorm2d or PositionNormUncentered2d, with or without bias), BcosConv2d with B = 2 fixed
+and max_out = 1, eval mode.  Anything else -- the `_bnu` variants, a learnable or other B, MaxOut, a model in train() -- makes attach() raise BcosHipError; the module
 path keeps working for them.  `occlude=`, `perturb=`, `rise=` (forward) and `functional=` (explain), explain_targets and
 explain_functionals come with the base class and the shared head and are supported; replayed `gates=` (there is no ReLU) and `cotangent=`
 (no attention-pool head) are refused with a message.
@@ -83,13 +84,16 @@ def _conv(conv, name, scale=None):
 
 
 class _PosNorm:
-    """Kernel-side view of a DetachablePositionNorm2d: LayerNorm over the rows of the NHWC image."""
+    """Kernel-side view of a DetachablePositionNorm2d -- LayerNorm over the rows of the NHWC image -- or of a PositionNormUncentered2d:
+    the same rows, the same launches, the uncentered kernels (csrc/bcos_unorm.hip: x itself is divided, and the detached gradient
+    subtracts no mean)."""
 
     def __init__(self, norm, name):
-        if type(norm).__name__ != "DetachablePositionNorm2d":
+        if type(norm).__name__ not in ("DetachablePositionNorm2d", "PositionNormUncentered2d"):
             raise BcosHipError(f"convnext engine: `{name}` is a {type(norm).__name__}; the plan takes the position-norm variants only "
                                "(DetachablePositionNorm2d; the `_bnu` variants run through the module path)")
         self.module, self.name = norm, name
+        self.unc = type(norm).__name__ == "PositionNormUncentered2d"
         self.refresh()
 
     def fingerprint(self):
@@ -109,14 +113,15 @@ class _PosNorm:
 
     def fwd(self, x, keep):
         _log("pn", self.name)
-        y, rstd = ops.layernorm_fwd(x.view(-1, self.C), self.w, self.b, self.eps, want_rstd=keep)
+        y, rstd = (ops.layernorm_unc_fwd if self.unc else ops.layernorm_fwd)(x.view(-1, self.C), self.w, self.b, self.eps, want_rstd=keep)
         return _nhwc(y, x), rstd
 
     def bwd(self, g, rstd, mul2=None, want_out=True):
         """detached gradient of the norm -> (gradient, gradient * mul2 or None)"""
         _log("pn_bwd", self.name)
-        o, o2 = ops.layernorm_bwd_detached(g.view(-1, self.C), self.w, rstd, mul2=None if mul2 is None else mul2.view(-1, self.C),
-                                           want_out=want_out, want_out2=mul2 is not None)
+        bwd = ops.layernorm_unc_bwd_detached if self.unc else ops.layernorm_bwd_detached
+        o, o2 = bwd(g.view(-1, self.C), self.w, rstd, mul2=None if mul2 is None else mul2.view(-1, self.C), want_out=want_out,
+                    want_out2=mul2 is not None)
         return (None if o is None else _nhwc(o, g)), (None if o2 is None else _nhwc(o2, g))
 
 

@@ -20,7 +20,7 @@ CSRC = PKG_ROOT / "csrc"
 INCLUDE = REPO_ROOT / "include"
 SOURCES = ["bcos_tapconv.hip", "bcos_tapconv_dispatch.hip", "bcos_weights.hip", "bcos_absmax.hip", "bcos_skinny.hip", "bcos_elementwise.hip", "bcos_vit.hip", "bcos_render.hip", "bcos_train.hip",
            "bcos_agc.hip", "bcos_occlusion.hip", "bcos_rise.hip", "bcos_perturb.hip", "bcos_head.hip", "bcos_boundary.hip", "bcos_shortcut.hip", "bcos_stem.hip", "bcos_dense.hip", "bcos_siglip.hip",
-           "bcos_dwconv.hip", "bcos_dwconv_train.hip", "bcos_abi.hip"]
+           "bcos_dwconv.hip", "bcos_dwconv_train.hip", "bcos_unorm.hip", "bcos_abi.hip"]
 # every header a source may include -- all of csrc/*.h and the ABI header: an edit of any of them rebuilds every object
 HEADERS = sorted(CSRC.glob("*.h")) + [INCLUDE / "bcos_hip.h"]
 
@@ -240,6 +240,12 @@ SIGNATURES = {
     "bcos_dwconv7_train_bwd": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P]),
     "bcos_dwconv7_wgrad": (C.c_int, [_P, _P, _F, _P, _P, _P, _L, _I, _I, _I, _I, _P]),
     "bcos_dwconv7_wgrad_workspace": (C.c_int, [_I, _I, _I, _I]),
+    "bcos_layernorm_unc_fwd": (C.c_int, [_P, _P, _P, _P, _P, _L, _I, _F, _P]),
+    "bcos_layernorm_unc_bwd_detached": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _L, _I, _P]),
+    "bcos_layernorm_unc_bwd": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _L, _I, _P]),
+    "bcos_groupnorm_unc_fwd": (C.c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P]),
+    "bcos_groupnorm_unc_bwd_detached": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "bcos_groupnorm_unc_bwd": (C.c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
 }
 
 _lib = None

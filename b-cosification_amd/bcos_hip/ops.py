@@ -2418,6 +2418,75 @@ def groupnorm_bwd_detached(gy_nhwc, groups, weight, rstd):
     return gx
 
 
+# ---- uncentered position / group norms (csrc/bcos_unorm.hip) ------------------------------------------------------------------
+def layernorm_unc_fwd(x2d, weight, bias, eps, want_rstd=False, out=None):
+    """y = weight x / sqrt(var + eps) + bias per row, var the CENTRED second moment (include/bcos_hip.h: bcos_layernorm_unc_fwd)
+    -> (y, rstd [rows] or None)."""
+    lib = _l.load()
+    rows, D = x2d.shape
+    y = out if out is not None else torch.empty_like(x2d)
+    rstd = torch.empty((rows,), device=x2d.device, dtype=torch.float32) if want_rstd else None
+    _l.check(lib.bcos_layernorm_unc_fwd(_dev(x2d, "x"), _dev(weight, "w"), _dev(bias, "b"), _dev(y, "y"), _dev(rstd, "rstd"),
+                                        rows, D, float(eps), _stream()), "bcos_layernorm_unc_fwd")
+    return y, rstd
+
+
+def layernorm_unc_bwd_detached(gy2d, weight, rstd, addend=None, mul2=None, want_out=True, want_out2=False, out=None):
+    """explanation mode: out = gy weight rstd (+ addend), out2 = out * mul2 -> (out, out2)"""
+    lib = _l.load()
+    rows, D = gy2d.shape
+    o = (out if out is not None else torch.empty_like(gy2d)) if want_out else None
+    o2 = torch.empty_like(gy2d) if want_out2 else None
+    _l.check(lib.bcos_layernorm_unc_bwd_detached(_dev(gy2d, "gy"), _dev(weight, "w"), _dev(rstd, "rstd"), _dev(addend, "addend"),
+                                                 _dev(mul2, "mul2"), _dev(o, "out"), _dev(o2, "out2"), rows, D, _stream()),
+             "bcos_layernorm_unc_bwd_detached")
+    return o, o2
+
+
+def layernorm_unc_bwd(gy2d, x2d, weight, rstd, want_xr=False, addend=None):
+    """training mode: the full input gradient (+ `addend`) and x rstd for the weight gradient -> (gx, xr or None)"""
+    lib = _l.load()
+    rows, D = gy2d.shape
+    gx = torch.empty_like(gy2d)
+    xr = torch.empty_like(gy2d) if want_xr else None
+    if addend is not None and tuple(addend.shape) != (rows, D):
+        raise BcosHipError(f"layernorm_unc_bwd: addend {tuple(addend.shape)} does not match {(rows, D)}")
+    _l.check(lib.bcos_layernorm_unc_bwd(_dev(gy2d, "gy"), _dev(x2d, "x"), _dev(weight, "weight"), _dev(rstd, "rstd"), _dev(addend, "addend"),
+                                        _dev(gx, "gx"), _dev(xr, "xr"), rows, D, _stream()), "bcos_layernorm_unc_bwd")
+    return gx, xr
+
+
+def groupnorm_unc_fwd(x_nhwc, groups, weight, bias, eps, want_rstd=False):
+    """Uncentered GroupNorm of an NHWC tensor [N,H,W,C] (include/bcos_hip.h: bcos_groupnorm_unc_fwd) -> (y, rstd [N*G] or None)."""
+    lib = _l.load()
+    N, H, W, Cc = x_nhwc.shape
+    y = torch.empty_like(x_nhwc)
+    rstd = torch.empty((N * groups,), device=x_nhwc.device, dtype=torch.float32) if want_rstd else None
+    _l.check(lib.bcos_groupnorm_unc_fwd(_dev(x_nhwc, "x"), _dev(weight, "weight"), _dev(bias, "bias"), _dev(y, "y"), _dev(rstd, "rstd"),
+                                        N, H * W, Cc, int(groups), float(eps), _stream()), "bcos_groupnorm_unc_fwd")
+    return y, rstd
+
+
+def groupnorm_unc_bwd_detached(gy_nhwc, groups, weight, rstd):
+    lib = _l.load()
+    N, H, W, Cc = gy_nhwc.shape
+    gx = torch.empty_like(gy_nhwc)
+    _l.check(lib.bcos_groupnorm_unc_bwd_detached(_dev(gy_nhwc, "gy"), _dev(weight, "weight"), _dev(rstd, "rstd"), _dev(gx, "gx"),
+                                                 N, H * W, Cc, int(groups), _stream()), "bcos_groupnorm_unc_bwd_detached")
+    return gx
+
+
+def groupnorm_unc_bwd(gy_nhwc, x_nhwc, groups, weight, rstd, want_xr=False):
+    """training mode -> (gx, xr = x rstd or None), include/bcos_hip.h: bcos_groupnorm_unc_bwd."""
+    lib = _l.load()
+    N, H, W, Cc = gy_nhwc.shape
+    gx = torch.empty_like(gy_nhwc)
+    xr = torch.empty_like(gy_nhwc) if want_xr else None
+    _l.check(lib.bcos_groupnorm_unc_bwd(_dev(gy_nhwc, "gy"), _dev(x_nhwc, "x"), _dev(weight, "weight"), _dev(rstd, "rstd"), _dev(gx, "gx"),
+                                        _dev(xr, "xr"), N, H * W, Cc, int(groups), _stream()), "bcos_groupnorm_unc_bwd")
+    return gx, xr
+
+
 def gelu_gate(x, want_gate=False, out=None):
     lib = _l.load()
     y = out if out is not None else torch.empty_like(x)

@@ -1410,6 +1410,63 @@ int bcos_dwconv7_wgrad(const float* gy, const float* mul, float gain, const floa
  * C % 4 != 0, or more than 2^31 - 1 bytes (C > 21396 at G = 256), which bcos_dwconv7_wgrad refuses as well. */
 int bcos_dwconv7_wgrad_workspace(int N, int H, int W, int C);
 
+/* -- uncentered position / group norms (csrc/bcos_unorm.hip; additive, ABI v12) ---------------------------------------------
+ * The norms of the B-cos v2 norm ablations whose variance is centred while the value that is divided is NOT: over a set S of n values
+ * (a row of x [rows, D] = the channels of a pixel of the NHWC image; an (image, group) of x [N, HW, C])
+ *     m = mean_S x,   var = mean_S (x - m)^2,   r = 1 / sqrt(var + eps),   y = weight x r + bias        (weight / bias may be NULL)
+ *     explanation mode (var a constant):   gx = h r,   h = gy weight                      -- no mean is subtracted
+ *     training mode:                       gx = r h - r^3 (x - m) (sum_S h x) / n
+ *     weight / bias gradients:             sum gy (x r),  sum gy                          (column reductions: bcos_colsum)
+ * Two-pass variance (the mean, then the centred squares); every reduction in one fixed order, no atomics, no workspace: a call repeated
+ * gives the same bits, and no output depends on which optional outputs were requested.
+ *
+ * Accuracy, per element (tests/unorm_cases.py, tests/test_unorm_gpu.py).  Against the same expressions in fp64 from the fp32 inputs
+ * (eps as the float passed; the gradients from the fp32 rstd they are GIVEN, not from an fp64 recomputation), with u = 2^-24,
+ * A = max_S |x|, sd = sqrt(var + eps), q = A / sd -- `x - m` is exact only to u A, which is a relative u A / sd in sd -- and d = x - m:
+ *     |y - y64|        <=  4.4 u ( |weight| |x / sd| (1 + q) + |y64| )
+ *     |rstd sd - 1|    <=  4.4 u ( 1 + q )
+ *     detached gradients, h = gy weight:
+ *     |out - out64|    <=  5.2 u ( |h rstd| + |addend| + |out64| ),     out2: that form times |mul2|, plus |out2_64|
+ *     full gradients, rs = rstd:
+ *     |gx - gx64|      <= 10.0 u ( rs |h| + rs^3 (|d| + A) mean_S |h x| + |addend| + |gx64| )
+ *     |xr_out - x rs|  <=  4.4 u |x rs|
+ * No term takes credit for cancellation: a row whose mean is 1000 x its spread, or a constant row (sd = sqrt(eps)), is held to the q term
+ * and no closer.  Each constant is 4 x the worst use of its form by a plain fp32 evaluation of the same expression (measured: y 1.015,
+ * rstd 1.046, detached 1.222, full 2.391, xr 0.999 u, each rounded up to the next tenth that leaves 2 %) over the test's case
+ * table (row widths 1 .. 1000 on both kernel forms, rows that leave wavefront groups partly empty, second passes of the grid-stride
+ * loops, misaligned views, offset / constant / outlier rows and rows decades apart; groups of 1 .. 18816 values, G = 1 .. C).
+ * BCOS_E_INVAL, before any HIP call: a NULL required pointer, a size <= 0; for the group form also C % G != 0. */
+
+/* Row form, one wavefront per row; 16-byte accesses where D % 4 == 0, D <= 256 and every tensor is 16-byte aligned, a strided loop
+ * otherwise.  Forward of PositionNormUncentered2d (bcos/modules/norms/uncentered_norms/posnorm_uncentered.py:39-58; the value does not
+ * depend on explanation mode); rstd_out (NULL or [rows]) keeps r for the backward. */
+int bcos_layernorm_unc_fwd(const float* x, const float* weight, const float* bias, float* y, float* rstd_out, int64_t rows, int D,
+                           float eps, void* stream);
+/* ... its explanation-mode input gradient (posnorm_uncentered.py:45-50 with `detach`): out = gy weight rstd (+ addend),
+ * out2 = out * mul2 (either output may be NULL, not both; mul2 NULL -> out2 = out): the contract of bcos_layernorm_bwd_detached
+ * without the row maxima. */
+int bcos_layernorm_unc_bwd_detached(const float* gy, const float* weight, const float* rstd, const float* addend, const float* mul2,
+                                    float* out, float* out2, int64_t rows, int D, void* stream);
+/* ... its training-mode input gradient (autograd of posnorm_uncentered.py:45-58 with `detach` off):
+ * gx = rs h - rs^3 (x - m) (sum h x) / D (+ addend); the mean is recomputed from the row; xr_out (NULL or [rows, D]) receives x rs for
+ * the weight gradient sum_rows gy (x rs) (bcos_colsum). */
+int bcos_layernorm_unc_bwd(const float* gy, const float* x, const float* weight, const float* rstd, const float* addend, float* gx,
+                           float* xr_out, int64_t rows, int D, void* stream);
+
+/* Group form on NHWC tensors x [N, HW, C], one workgroup per (image, group): group g owns channels [g C/G, (g+1) C/G) of every pixel.
+ * Forward of group_norm_uncentered / GroupNormUncentered2d (bcos/modules/norms/uncentered_norms/groupnorm_uncentered.py:21-61; G = C:
+ * GNInstanceNormUncentered2d :82-89, G = 1: GNLayerNormUncentered2d :92-99); rstd_out (NULL or [N*G]).  Arguments as bcos_groupnorm_fwd. */
+int bcos_groupnorm_unc_fwd(const float* x, const float* weight, const float* bias, float* y, float* rstd_out, int N, int HW, int C, int G,
+                           float eps, void* stream);
+/* ... explanation mode (groupnorm_uncentered.py:43-49 with `detach`): gx = gy weight rstd.  Arguments as bcos_groupnorm_bwd_detached. */
+int bcos_groupnorm_unc_bwd_detached(const float* gy, const float* weight, const float* rstd, float* gx, int N, int HW, int C, int G,
+                                    void* stream);
+/* ... training mode (autograd of groupnorm_uncentered.py:43-61 with `detach` off): per (image, group) of n = HW C / G values
+ * gx = rs h - rs^3 (x - m) (sum h x) / n; xr_out (NULL or like x) = x rs for the weight gradient.  Arguments as bcos_groupnorm_bwd, with
+ * xr_out in place of xhat_out. */
+int bcos_groupnorm_unc_bwd(const float* gy, const float* x, const float* weight, const float* rstd, float* gx, float* xr_out, int N,
+                           int HW, int C, int G, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
