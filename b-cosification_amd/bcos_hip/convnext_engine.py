@@ -85,7 +85,7 @@ def _conv(conv, name, scale=None):
 
 class _PosNorm:
     """Kernel-side view of a DetachablePositionNorm2d -- LayerNorm over the rows of the NHWC image -- or of a PositionNormUncentered2d:
-    the same rows, the same launches, the uncentered kernels (csrc/bcos_unorm.hip: x itself is divided, and the detached gradient
+    the same rows, the same launches, the uncentered kernels (csrc/bcos_norms.hip, centered=False: x itself is divided, and the detached gradient
     subtracts no mean)."""
 
     def __init__(self, norm, name):
@@ -94,6 +94,7 @@ class _PosNorm:
                                "(DetachablePositionNorm2d; the `_bnu` variants run through the module path)")
         self.module, self.name = norm, name
         self.unc = type(norm).__name__ == "PositionNormUncentered2d"
+        self.flavour = {"centered": False} if self.unc else {}         # (keywords of ops.layernorm_*: nothing for the centred norm)
         self.refresh()
 
     def fingerprint(self):
@@ -113,15 +114,14 @@ class _PosNorm:
 
     def fwd(self, x, keep):
         _log("pn", self.name)
-        y, rstd = (ops.layernorm_unc_fwd if self.unc else ops.layernorm_fwd)(x.view(-1, self.C), self.w, self.b, self.eps, want_rstd=keep)
+        y, rstd = ops.layernorm_fwd(x.view(-1, self.C), self.w, self.b, self.eps, want_rstd=keep, **self.flavour)
         return _nhwc(y, x), rstd
 
     def bwd(self, g, rstd, mul2=None, want_out=True):
         """detached gradient of the norm -> (gradient, gradient * mul2 or None)"""
         _log("pn_bwd", self.name)
-        bwd = ops.layernorm_unc_bwd_detached if self.unc else ops.layernorm_bwd_detached
-        o, o2 = bwd(g.view(-1, self.C), self.w, rstd, mul2=None if mul2 is None else mul2.view(-1, self.C), want_out=want_out,
-                    want_out2=mul2 is not None)
+        o, o2 = ops.layernorm_bwd_detached(g.view(-1, self.C), self.w, rstd, mul2=None if mul2 is None else mul2.view(-1, self.C),
+                                           want_out=want_out, want_out2=mul2 is not None, **self.flavour)
         return (None if o is None else _nhwc(o, g)), (None if o2 is None else _nhwc(o2, g))
 
 

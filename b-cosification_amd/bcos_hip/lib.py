@@ -18,9 +18,9 @@ REPO_ROOT = PKG_ROOT.parent
 LIB_PATH = Path(os.environ["BCOS_HIP_LIB"]) if os.environ.get("BCOS_HIP_LIB") else PKG_ROOT / "lib" / "libbcos_hip.so"
 CSRC = PKG_ROOT / "csrc"
 INCLUDE = REPO_ROOT / "include"
-SOURCES = ["bcos_tapconv.hip", "bcos_tapconv_dispatch.hip", "bcos_weights.hip", "bcos_absmax.hip", "bcos_skinny.hip", "bcos_elementwise.hip", "bcos_vit.hip", "bcos_render.hip", "bcos_train.hip",
+SOURCES = ["bcos_tapconv.hip", "bcos_tapconv_dispatch.hip", "bcos_weights.hip", "bcos_absmax.hip", "bcos_skinny.hip", "bcos_elementwise.hip", "bcos_vit.hip", "bcos_norms.hip", "bcos_render.hip", "bcos_train.hip",
            "bcos_agc.hip", "bcos_occlusion.hip", "bcos_rise.hip", "bcos_perturb.hip", "bcos_head.hip", "bcos_boundary.hip", "bcos_shortcut.hip", "bcos_stem.hip", "bcos_dense.hip", "bcos_siglip.hip",
-           "bcos_dwconv.hip", "bcos_dwconv_train.hip", "bcos_unorm.hip", "bcos_abi.hip"]
+           "bcos_dwconv.hip", "bcos_dwconv_train.hip", "bcos_abi.hip"]
 # every header a source may include -- all of csrc/*.h and the ABI header: an edit of any of them rebuilds every object
 HEADERS = sorted(CSRC.glob("*.h")) + [INCLUDE / "bcos_hip.h"]
 

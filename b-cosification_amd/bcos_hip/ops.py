@@ -2314,26 +2314,42 @@ def channel_axpby(a, sa, b=None, mb=None, sb=None, out=None):
     return out
 
 
-# ---- transformer pieces (csrc/bcos_vit.hip) ----------------------------------------------------------------
+# ---- row and group norms, centred and uncentered (csrc/bcos_norms.hip) ---------------------------------------------------
+# One wrapper per operation.  `centered=True`: y = weight (x - mean) rstd + bias (LayerNorm / GroupNorm); `centered=False`: the uncentered
+# norms of the B-cos v2 ablations, y = weight x rstd + bias -- the same centred variance, the value itself divided (the `_unc` entry points).
 def _am_ptr(am):
     return C.c_void_p(am.data_ptr()) if am is not None else None
 
 
-def layernorm_fwd(x2d, weight, bias, eps, want_rstd=False, out=None, want_absmax=False):
-    """`want_absmax`: the kernel also emits the row maxima of y for the split-f16 contraction that reads it."""
+def _norm_entry(lib, kind, step, centered):
+    """(entry point, its name) of a step ("fwd", "bwd_detached", "bwd") of the "layer" / "group" norm in the asked flavour"""
+    name = f"bcos_{kind}norm_{step}" if centered else f"bcos_{kind}norm_unc_{step}"
+    return getattr(lib, name), name
+
+
+def _no_row_maxima(who):
+    """the row maxima are outputs of the centred entry points alone: the uncentered ABI has none, and a second launch would not be them"""
+    return BcosHipError(f"{who}: want_absmax / want_absmax2 need centered=True (the uncentered entry point has no such output)")
+
+
+def layernorm_fwd(x2d, weight, bias, eps, want_rstd=False, out=None, want_absmax=False, centered=True):
+    """Norm over the rows of x2d [rows, D] (include/bcos_hip.h: bcos_layernorm_fwd / bcos_layernorm_unc_fwd) -> (y, rstd [rows] or None).
+    `want_absmax` (centred only): the kernel also emits the row maxima of y for the split-f16 contraction that reads it."""
     lib = _l.load()
+    if want_absmax and not centered:
+        raise _no_row_maxima("layernorm_fwd")
     rows, D = x2d.shape
     y = out if out is not None else torch.empty_like(x2d)
     rstd = torch.empty((rows,), device=x2d.device, dtype=torch.float32) if want_rstd else None
-    am = _fused_absmax(y, want_absmax)
-    _l.check(lib.bcos_layernorm_fwd(_dev(x2d, "x"), _dev(weight, "w"), _dev(bias, "b"), _dev(y, "y"), _dev(rstd, "rstd"), _am_ptr(am),
-                                    rows, D, float(eps), _stream()), "bcos_layernorm_fwd")
+    fn, name = _norm_entry(lib, "layer", "fwd", centered)
+    am = (_am_ptr(_fused_absmax(y, want_absmax)),) if centered else ()
+    _l.check(fn(_dev(x2d, "x"), _dev(weight, "w"), _dev(bias, "b"), _dev(y, "y"), _dev(rstd, "rstd"), *am, rows, D, float(eps), _stream()), name)
     return y, rstd
 
 
 def layernorm_stats(x2d, weight, bias, eps, want_zsumsq=False, want_absmax=False):
     """Row statistics of a LayerNorm whose output is never written (include/bcos_hip.h: bcos_layernorm_stats): (rstd, |y|^2 or None);
-    `want_absmax`: x2d gets its operand maxima attached (the contraction that follows reads x2d itself)."""
+    `want_absmax`: x2d gets its operand maxima attached (the contraction that follows reads x2d itself).  Centred only."""
     lib = _l.load()
     rows, D = x2d.shape
     rstd = torch.empty((rows,), device=x2d.device, dtype=torch.float32)
@@ -2344,43 +2360,75 @@ def layernorm_stats(x2d, weight, bias, eps, want_zsumsq=False, want_absmax=False
     return rstd, zss
 
 
-def layernorm_bwd_detached(gy2d, weight, rstd, addend=None, mul2=None, want_out=True, want_out2=False, out=None, want_absmax2=False):
+def layernorm_bwd_detached(gy2d, weight, rstd, addend=None, mul2=None, want_out=True, want_out2=False, out=None, want_absmax2=False,
+                           centered=True):
+    """explanation mode (variance a constant): out = h - mean(h) centred, h uncentered, h = gy weight rstd (+ addend); out2 = out * mul2
+    -> (out, out2).  `want_absmax2` (centred only): the row maxima of out2."""
     lib = _l.load()
+    if want_absmax2 and not centered:
+        raise _no_row_maxima("layernorm_bwd_detached")
     rows, D = gy2d.shape
     o = (out if out is not None else torch.empty_like(gy2d)) if want_out else None
     o2 = torch.empty_like(gy2d) if want_out2 else None
-    am = _fused_absmax(o2, want_absmax2) if o2 is not None else None
-    _l.check(lib.bcos_layernorm_bwd_detached(_dev(gy2d, "gy"), _dev(weight, "w"), _dev(rstd, "rstd"), _dev(addend, "addend"),
-                                             _dev(mul2, "mul2"), _dev(o, "out"), _dev(o2, "out2"), _am_ptr(am), rows, D, _stream()),
-             "bcos_layernorm_bwd_detached")
+    fn, name = _norm_entry(lib, "layer", "bwd_detached", centered)
+    am = (_am_ptr(_fused_absmax(o2, want_absmax2) if o2 is not None else None),) if centered else ()
+    _l.check(fn(_dev(gy2d, "gy"), _dev(weight, "w"), _dev(rstd, "rstd"), _dev(addend, "addend"), _dev(mul2, "mul2"), _dev(o, "out"),
+                _dev(o2, "out2"), *am, rows, D, _stream()), name)
     return o, o2
 
 
-def layernorm_bwd(gy2d, x2d, weight, rstd, want_xhat=False, addend=None):
-    """Full LayerNorm input gradient (+ x_hat for the weight gradient; + `addend`, the residual stream's gradient),
-    include/bcos_hip.h: bcos_layernorm_bwd_add."""
+def layernorm_bwd(gy2d, x2d, weight, rstd, want_xhat=False, addend=None, centered=True):
+    """training mode: the full input gradient (+ `addend`, the residual stream's gradient), include/bcos_hip.h: bcos_layernorm_bwd_add /
+    bcos_layernorm_unc_bwd -> (gx, second result or None).  `want_xhat` asks for what the weight gradient multiplies gy by: x_hat =
+    (x - mean) rstd when centred, x rstd when not."""
     lib = _l.load()
     rows, D = gy2d.shape
     gx = torch.empty_like(gy2d)
     xhat = torch.empty_like(gy2d) if want_xhat else None
     if addend is not None and tuple(addend.shape) != (rows, D):
         raise BcosHipError(f"layernorm_bwd: addend {tuple(addend.shape)} does not match {(rows, D)}")
-    _l.check(lib.bcos_layernorm_bwd_add(_dev(gy2d, "gy"), _dev(x2d, "x"), _dev(weight, "weight"), _dev(rstd, "rstd"), _dev(addend, "addend"),
-                                        _dev(gx, "gx"), _dev(xhat, "xhat"), rows, D, _stream()), "bcos_layernorm_bwd")
+    fn, name = (lib.bcos_layernorm_bwd_add, "bcos_layernorm_bwd") if centered else (lib.bcos_layernorm_unc_bwd, "bcos_layernorm_unc_bwd")
+    _l.check(fn(_dev(gy2d, "gy"), _dev(x2d, "x"), _dev(weight, "weight"), _dev(rstd, "rstd"), _dev(addend, "addend"), _dev(gx, "gx"),
+                _dev(xhat, "xhat"), rows, D, _stream()), name)
     return gx, xhat
 
 
-def groupnorm_bwd(gy_nhwc, x_nhwc, groups, weight, rstd, want_xhat=False):
-    """Full GroupNorm input gradient (+ x_hat for the affine gradients), include/bcos_hip.h: bcos_groupnorm_bwd."""
+def groupnorm_fwd(x_nhwc, groups, weight, bias, eps, want_rstd=False, centered=True):
+    """Group norm of an NHWC tensor [N,H,W,C] (include/bcos_hip.h: bcos_groupnorm_fwd / bcos_groupnorm_unc_fwd) -> (y, rstd [N*G] or None)."""
+    lib = _l.load()
+    N, H, W, Cc = x_nhwc.shape
+    y = torch.empty_like(x_nhwc)
+    rstd = torch.empty((N * groups,), device=x_nhwc.device, dtype=torch.float32) if want_rstd else None
+    fn, name = _norm_entry(lib, "group", "fwd", centered)
+    _l.check(fn(_dev(x_nhwc, "x"), _dev(weight, "weight"), _dev(bias, "bias"), _dev(y, "y"), _dev(rstd, "rstd"), N, H * W, Cc, int(groups),
+                float(eps), _stream()), name)
+    return y, rstd
+
+
+def groupnorm_bwd_detached(gy_nhwc, groups, weight, rstd, centered=True):
+    """explanation mode: gx = h - mean_group(h) centred, h uncentered, h = gy weight rstd"""
+    lib = _l.load()
+    N, H, W, Cc = gy_nhwc.shape
+    gx = torch.empty_like(gy_nhwc)
+    fn, name = _norm_entry(lib, "group", "bwd_detached", centered)
+    _l.check(fn(_dev(gy_nhwc, "gy"), _dev(weight, "weight"), _dev(rstd, "rstd"), _dev(gx, "gx"), N, H * W, Cc, int(groups), _stream()), name)
+    return gx
+
+
+def groupnorm_bwd(gy_nhwc, x_nhwc, groups, weight, rstd, want_xhat=False, centered=True):
+    """training mode: the full input gradient, include/bcos_hip.h: bcos_groupnorm_bwd / bcos_groupnorm_unc_bwd -> (gx, second result or
+    None).  `want_xhat` asks for what the affine gradients multiply gy by: x_hat when centred, x rstd when not."""
     lib = _l.load()
     N, H, W, Cc = gy_nhwc.shape
     gx = torch.empty_like(gy_nhwc)
     xhat = torch.empty_like(gy_nhwc) if want_xhat else None
-    _l.check(lib.bcos_groupnorm_bwd(_dev(gy_nhwc, "gy"), _dev(x_nhwc, "x"), _dev(weight, "weight"), _dev(rstd, "rstd"), _dev(gx, "gx"),
-                                    _dev(xhat, "xhat"), N, H * W, Cc, int(groups), _stream()), "bcos_groupnorm_bwd")
+    fn, name = _norm_entry(lib, "group", "bwd", centered)
+    _l.check(fn(_dev(gy_nhwc, "gy"), _dev(x_nhwc, "x"), _dev(weight, "weight"), _dev(rstd, "rstd"), _dev(gx, "gx"), _dev(xhat, "xhat"),
+                N, H * W, Cc, int(groups), _stream()), name)
     return gx, xhat
 
 
+# ---- transformer pieces (csrc/bcos_vit.hip) ----------------------------------------------------------------
 def gelu_bwd(gy, x):
     lib = _l.load()
     gx = torch.empty_like(gy)
@@ -2396,95 +2444,6 @@ def attention_bwd(qkv, stats, out, gout, heads, scale):
     _l.check(lib.bcos_attention_bwd(_dev(qkv, "qkv"), _dev(stats, "stats"), _dev(out, "out"), _dev(gout, "gout"), _dev(gqkv, "gqkv"),
                                     B, T, heads, three_inner // (3 * heads), float(scale), _stream()), "bcos_attention_bwd")
     return gqkv
-
-
-def groupnorm_fwd(x_nhwc, groups, weight, bias, eps, want_rstd=False):
-    """GroupNorm of an NHWC tensor [N,H,W,C] (include/bcos_hip.h: bcos_groupnorm_fwd) -> (y, rstd [N*G] or None)."""
-    lib = _l.load()
-    N, H, W, Cc = x_nhwc.shape
-    y = torch.empty_like(x_nhwc)
-    rstd = torch.empty((N * groups,), device=x_nhwc.device, dtype=torch.float32) if want_rstd else None
-    _l.check(lib.bcos_groupnorm_fwd(_dev(x_nhwc, "x"), _dev(weight, "weight"), _dev(bias, "bias"), _dev(y, "y"), _dev(rstd, "rstd"),
-                                    N, H * W, Cc, int(groups), float(eps), _stream()), "bcos_groupnorm_fwd")
-    return y, rstd
-
-
-def groupnorm_bwd_detached(gy_nhwc, groups, weight, rstd):
-    lib = _l.load()
-    N, H, W, Cc = gy_nhwc.shape
-    gx = torch.empty_like(gy_nhwc)
-    _l.check(lib.bcos_groupnorm_bwd_detached(_dev(gy_nhwc, "gy"), _dev(weight, "weight"), _dev(rstd, "rstd"), _dev(gx, "gx"),
-                                             N, H * W, Cc, int(groups), _stream()), "bcos_groupnorm_bwd_detached")
-    return gx
-
-
-# ---- uncentered position / group norms (csrc/bcos_unorm.hip) ------------------------------------------------------------------
-def layernorm_unc_fwd(x2d, weight, bias, eps, want_rstd=False, out=None):
-    """y = weight x / sqrt(var + eps) + bias per row, var the CENTRED second moment (include/bcos_hip.h: bcos_layernorm_unc_fwd)
-    -> (y, rstd [rows] or None)."""
-    lib = _l.load()
-    rows, D = x2d.shape
-    y = out if out is not None else torch.empty_like(x2d)
-    rstd = torch.empty((rows,), device=x2d.device, dtype=torch.float32) if want_rstd else None
-    _l.check(lib.bcos_layernorm_unc_fwd(_dev(x2d, "x"), _dev(weight, "w"), _dev(bias, "b"), _dev(y, "y"), _dev(rstd, "rstd"),
-                                        rows, D, float(eps), _stream()), "bcos_layernorm_unc_fwd")
-    return y, rstd
-
-
-def layernorm_unc_bwd_detached(gy2d, weight, rstd, addend=None, mul2=None, want_out=True, want_out2=False, out=None):
-    """explanation mode: out = gy weight rstd (+ addend), out2 = out * mul2 -> (out, out2)"""
-    lib = _l.load()
-    rows, D = gy2d.shape
-    o = (out if out is not None else torch.empty_like(gy2d)) if want_out else None
-    o2 = torch.empty_like(gy2d) if want_out2 else None
-    _l.check(lib.bcos_layernorm_unc_bwd_detached(_dev(gy2d, "gy"), _dev(weight, "w"), _dev(rstd, "rstd"), _dev(addend, "addend"),
-                                                 _dev(mul2, "mul2"), _dev(o, "out"), _dev(o2, "out2"), rows, D, _stream()),
-             "bcos_layernorm_unc_bwd_detached")
-    return o, o2
-
-
-def layernorm_unc_bwd(gy2d, x2d, weight, rstd, want_xr=False, addend=None):
-    """training mode: the full input gradient (+ `addend`) and x rstd for the weight gradient -> (gx, xr or None)"""
-    lib = _l.load()
-    rows, D = gy2d.shape
-    gx = torch.empty_like(gy2d)
-    xr = torch.empty_like(gy2d) if want_xr else None
-    if addend is not None and tuple(addend.shape) != (rows, D):
-        raise BcosHipError(f"layernorm_unc_bwd: addend {tuple(addend.shape)} does not match {(rows, D)}")
-    _l.check(lib.bcos_layernorm_unc_bwd(_dev(gy2d, "gy"), _dev(x2d, "x"), _dev(weight, "weight"), _dev(rstd, "rstd"), _dev(addend, "addend"),
-                                        _dev(gx, "gx"), _dev(xr, "xr"), rows, D, _stream()), "bcos_layernorm_unc_bwd")
-    return gx, xr
-
-
-def groupnorm_unc_fwd(x_nhwc, groups, weight, bias, eps, want_rstd=False):
-    """Uncentered GroupNorm of an NHWC tensor [N,H,W,C] (include/bcos_hip.h: bcos_groupnorm_unc_fwd) -> (y, rstd [N*G] or None)."""
-    lib = _l.load()
-    N, H, W, Cc = x_nhwc.shape
-    y = torch.empty_like(x_nhwc)
-    rstd = torch.empty((N * groups,), device=x_nhwc.device, dtype=torch.float32) if want_rstd else None
-    _l.check(lib.bcos_groupnorm_unc_fwd(_dev(x_nhwc, "x"), _dev(weight, "weight"), _dev(bias, "bias"), _dev(y, "y"), _dev(rstd, "rstd"),
-                                        N, H * W, Cc, int(groups), float(eps), _stream()), "bcos_groupnorm_unc_fwd")
-    return y, rstd
-
-
-def groupnorm_unc_bwd_detached(gy_nhwc, groups, weight, rstd):
-    lib = _l.load()
-    N, H, W, Cc = gy_nhwc.shape
-    gx = torch.empty_like(gy_nhwc)
-    _l.check(lib.bcos_groupnorm_unc_bwd_detached(_dev(gy_nhwc, "gy"), _dev(weight, "weight"), _dev(rstd, "rstd"), _dev(gx, "gx"),
-                                                 N, H * W, Cc, int(groups), _stream()), "bcos_groupnorm_unc_bwd_detached")
-    return gx
-
-
-def groupnorm_unc_bwd(gy_nhwc, x_nhwc, groups, weight, rstd, want_xr=False):
-    """training mode -> (gx, xr = x rstd or None), include/bcos_hip.h: bcos_groupnorm_unc_bwd."""
-    lib = _l.load()
-    N, H, W, Cc = gy_nhwc.shape
-    gx = torch.empty_like(gy_nhwc)
-    xr = torch.empty_like(gy_nhwc) if want_xr else None
-    _l.check(lib.bcos_groupnorm_unc_bwd(_dev(gy_nhwc, "gy"), _dev(x_nhwc, "x"), _dev(weight, "weight"), _dev(rstd, "rstd"), _dev(gx, "gx"),
-                                        _dev(xr, "xr"), N, H * W, Cc, int(groups), _stream()), "bcos_groupnorm_unc_bwd")
-    return gx, xr
 
 
 def gelu_gate(x, want_gate=False, out=None):

@@ -4,7 +4,7 @@ The reference trains its ViTs with the same modules it explains them with (bcos/
 bcos/models/vit.py:143-228, bcosifylinear.py:61-94, centered_norms.py:187-245, bcosify_vit.py:27-32; nothing detached).  With a
 ViTEngine attached, `net.train(); net(x)` is ONE autograd node whose forward / backward walk the engine's block list and issue the HIP
 launches directly on [rows, dim] token matrices -- the per-layer path's arithmetic launch for launch (bcos/modules/_hipfn.py:
-BcosLinearFn, centered_norms.py: _LayerNormFn, bcos/models/vit.py: _AttentionCoreFn, bcosify_vit.py: _GeluFn), without one autograd
+BcosLinearFn, norms/_norm_fns.py: _RowNormFn, bcos/models/vit.py: _AttentionCoreFn, bcosify_vit.py: _GeluFn), without one autograd
 node, one module call and one set of reshapes per layer, with the operand maxima of every contraction operand coming out of the
 launch that writes it (so forward and input-gradient contractions run the 3-product split-f16 loop), and one zero fill per pass for
 all of them.

@@ -1,15 +1,14 @@
-// bcos_vit.hip -- the non-B-cos pieces of B-cosified transformers on gfx950:
-// DetachableLayerNorm (bcos/modules/norms/centered_norms.py:187-245), MyGELU (bcosify_vit.py:27-32), the softmax
-// attention of bcos/models/vit.py:143-158 / bcos/modules/bcosattnpool.py:22-59 with q,k detached in explanation
-// mode, the token positional-embedding add and the un-patchify end of the ViT explanation pass.
-// LayerNorm / GELU / embedding add are streaming kernels (one wavefront per LayerNorm row); the attention runs on fp32
+// bcos_vit.hip -- the non-B-cos pieces of B-cosified transformers on gfx950: MyGELU (bcosify_vit.py:27-32), the
+// softmax attention of bcos/models/vit.py:143-158 / bcos/modules/bcosattnpool.py:22-59 with q,k detached in explanation
+// mode, the token positional-embedding add and the un-patchify end of the ViT explanation pass.  (The LayerNorm / GroupNorm
+// kernels of the same networks live in bcos_norms.hip, with the uncentered norms.)
+// GELU / embedding add are streaming kernels; the attention runs on fp32
 // MFMA, one workgroup per (image, head), with the walked operand and the transposed value operand resident in LDS and
 // the probabilities kept in registers between the two products.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <math.h>
 #include <stdlib.h>
-#include <initializer_list>
 #include <atomic>
 #include "bcos_hip.h"
 #include "bcos_internal.h"
@@ -18,232 +17,6 @@
 namespace {
 
 constexpr int TPB = 256;
-
-// ---- LayerNorm over the last dimension, one wavefront per row -----------------------------------------------
-// Rows of up to 256 floats (D % 4 == 0): the row lives in ONE float4 per lane -- read once, two wavefront reductions, written
-// once, 16-byte accesses -- and the row's max |y| (what the split-f16 contraction reading y scales its operand by) falls out
-// of the registers.  Other widths take the strided loop.
-template <bool VEC>
-__global__ __launch_bounds__(TPB) void layernorm_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
-                                                            const float* __restrict__ b, float* __restrict__ y,
-                                                            float* __restrict__ rstd_out, unsigned* __restrict__ absmax_out,
-                                                            int64_t rows, int D, float eps) {
-    const int lane = threadIdx.x & 63;
-    const int64_t wave = ((int64_t)blockIdx.x * TPB + threadIdx.x) >> 6;
-    const int64_t nwaves = ((int64_t)gridDim.x * TPB) >> 6;
-    if constexpr (VEC) {
-        const bool on = lane * 4 < D;
-        f32x4 wv = {1.f, 1.f, 1.f, 1.f}, bv = {0.f, 0.f, 0.f, 0.f};
-        if (on && w) wv = *reinterpret_cast<const f32x4*>(w + lane * 4);
-        if (on && b) bv = *reinterpret_cast<const f32x4*>(b + lane * 4);
-        for (int64_t r = wave; r < rows; r += nwaves) {
-            f32x4 v = {0.f, 0.f, 0.f, 0.f};
-            if (on) v = *reinterpret_cast<const f32x4*>(x + r * D + lane * 4);
-            const float mean = wave_sum((v[0] + v[1]) + (v[2] + v[3])) / (float)D;
-            f32x4 d = v - mean;
-            if (!on) d = f32x4{0.f, 0.f, 0.f, 0.f};
-            const float var = wave_sum(fmaf(d[0], d[0], d[1] * d[1]) + fmaf(d[2], d[2], d[3] * d[3])) / (float)D;
-            const float sd = sqrtf(var + eps);
-            f32x4 o = {d[0] / sd, d[1] / sd, d[2] / sd, d[3] / sd};
-            o = o * wv + bv;
-            if (on) *reinterpret_cast<f32x4*>(y + r * D + lane * 4) = o;
-            if (rstd_out && lane == 0) rstd_out[r] = 1.0f / sd;
-            if (absmax_out) {
-                const unsigned m = wave_max_u32(on ? absbits4(o) : 0u);
-                if (lane == 0) absmax_out[r] = m;
-            }
-        }
-    } else {
-        for (int64_t r = wave; r < rows; r += nwaves) {
-            const float* src = x + r * D;
-            float s = 0.f;
-            for (int c = lane; c < D; c += 64) s += src[c];
-            const float mean = wave_sum(s) / (float)D;
-            float v = 0.f;
-            for (int c = lane; c < D; c += 64) { const float d = src[c] - mean; v = fmaf(d, d, v); }
-            const float var = wave_sum(v) / (float)D;
-            const float sd = sqrtf(var + eps);
-            float* dst = y + r * D;
-            unsigned m = 0u;
-            for (int c = lane; c < D; c += 64) {
-                float o = (src[c] - mean) / sd;
-                if (w) o *= w[c];
-                if (b) o += b[c];
-                dst[c] = o;
-                m = max(m, __float_as_uint(o) & 0x7fffffffu);
-            }
-            if (rstd_out && lane == 0) rstd_out[r] = 1.0f / sd;
-            if (absmax_out) {
-                m = wave_max_u32(m);
-                if (lane == 0) absmax_out[r] = m;
-            }
-        }
-    }
-}
-
-// Row statistics of the LayerNorm for a contraction that reads x itself (bcos_epilogue.row_scale / a_sumsq): same reductions as
-// layernorm_fwd_kernel (mean, then the centered second moment), plus |gamma xhat + beta|^2 and max |x|; nothing row-sized is written.
-__global__ __launch_bounds__(TPB) void layernorm_stats_kernel(const float* __restrict__ x, const float* __restrict__ w,
-                                                              const float* __restrict__ b, float* __restrict__ rstd_out,
-                                                              float* __restrict__ zss_out, unsigned* __restrict__ absmax_out,
-                                                              int64_t rows, int D, float eps) {
-    const int lane = threadIdx.x & 63;
-    const int64_t wave = ((int64_t)blockIdx.x * TPB + threadIdx.x) >> 6;
-    const int64_t nwaves = ((int64_t)gridDim.x * TPB) >> 6;
-    for (int64_t r = wave; r < rows; r += nwaves) {
-        const float* src = x + r * D;
-        float s = 0.f;
-        unsigned m = 0u;
-        for (int c = lane; c < D; c += 64) { s += src[c]; m = max(m, __float_as_uint(src[c]) & 0x7fffffffu); }
-        const float mean = wave_sum(s) / (float)D;
-        float v = 0.f;
-        for (int c = lane; c < D; c += 64) { const float d = src[c] - mean; v = fmaf(d, d, v); }
-        const float var = wave_sum(v) / (float)D;
-        const float sd = sqrtf(var + eps);
-        if (lane == 0) rstd_out[r] = 1.0f / sd;
-        if (zss_out) {
-            float zs = 0.f;
-            for (int c = lane; c < D; c += 64) {
-                float o = (src[c] - mean) / sd;
-                if (w) o *= w[c];
-                if (b) o += b[c];
-                zs = fmaf(o, o, zs);
-            }
-            zs = wave_sum(zs);
-            if (lane == 0) zss_out[r] = zs;
-        }
-        if (absmax_out) {
-            m = wave_max_u32(m);
-            if (lane == 0) absmax_out[r] = m;
-        }
-    }
-}
-
-// The same statistics for rows of up to 256 floats (D % 4 == 0), SIXTEEN lanes per row: a wavefront holds four rows at once (NV
-// 16-byte pieces per lane, four-step reductions), so a workgroup keeps 16 rows of loads in flight where the one-row-per-wavefront
-// form above keeps four -- the kernel is one dependent chain per row (load, mean, centred moment, output norm) and nothing else.
-__device__ inline float sum16(float v) {
-#pragma unroll
-    for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-template <int NV>
-__global__ __launch_bounds__(TPB) void layernorm_stats16_kernel(const float* __restrict__ x, const float* __restrict__ w,
-                                                                const float* __restrict__ b, float* __restrict__ rstd_out,
-                                                                float* __restrict__ zss_out, unsigned* __restrict__ absmax_out,
-                                                                int64_t rows, int D, float eps) {
-    const int lane = threadIdx.x & 63, sub = lane & 15, grp = lane >> 4;
-    const int64_t wave = ((int64_t)blockIdx.x * TPB + threadIdx.x) >> 6;
-    const int64_t nwaves = ((int64_t)gridDim.x * TPB) >> 6;
-    f32x4 wv[NV], bv[NV];
-    bool on[NV];
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const int c = (sub + 16 * i) * 4;
-        on[i] = c < D;
-        wv[i] = (on[i] && w) ? *reinterpret_cast<const f32x4*>(w + c) : f32x4{1.f, 1.f, 1.f, 1.f};
-        bv[i] = (on[i] && b) ? *reinterpret_cast<const f32x4*>(b + c) : f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-    for (int64_t r0 = wave * 4; r0 < rows; r0 += nwaves * 4) {
-        const int64_t r = r0 + grp;
-        const bool live = r < rows;
-        f32x4 v[NV];
-        float s = 0.f;
-        unsigned m = 0u;
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            v[i] = (live && on[i]) ? *reinterpret_cast<const f32x4*>(x + r * D + (sub + 16 * i) * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
-            s += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
-            m = max(m, absbits4(v[i]));
-        }
-        const float mean = sum16(s) / (float)D;
-        float q = 0.f;
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            v[i] = on[i] ? v[i] - mean : f32x4{0.f, 0.f, 0.f, 0.f};
-            q += fmaf(v[i][0], v[i][0], v[i][1] * v[i][1]) + fmaf(v[i][2], v[i][2], v[i][3] * v[i][3]);
-        }
-        const float sd = sqrtf(sum16(q) / (float)D + eps);
-        if (sub == 0 && live) rstd_out[r] = 1.0f / sd;
-        if (zss_out) {
-            float zs = 0.f;
-#pragma unroll
-            for (int i = 0; i < NV; ++i) {
-                f32x4 o = {v[i][0] / sd, v[i][1] / sd, v[i][2] / sd, v[i][3] / sd};       // (the value layernorm_fwd_kernel writes)
-                o = o * wv[i] + bv[i];
-                if (!on[i]) o = f32x4{0.f, 0.f, 0.f, 0.f};
-                zs += fmaf(o[0], o[0], o[1] * o[1]) + fmaf(o[2], o[2], o[3] * o[3]);
-            }
-            zs = sum16(zs);
-            if (sub == 0 && live) zss_out[r] = zs;
-        }
-        if (absmax_out) {
-#pragma unroll
-            for (int o = 8; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o));
-            if (sub == 0 && live) absmax_out[r] = m;
-        }
-    }
-}
-
-// explanation mode: the variance is a constant, the mean is not (centered_norms.py:204-215):
-//   y = w * (x - mean(x)) / std   =>   gx = h - mean(h),  h = gy * w / std
-// out = gx (+ addend); out2 = out * mul2 (the scale of the B-cos layer that produced x), both optional extras.
-template <bool VEC>
-__global__ __launch_bounds__(TPB) void layernorm_bwd_detached_kernel(const float* __restrict__ gy,
-                                                                     const float* __restrict__ w,
-                                                                     const float* __restrict__ rstd,
-                                                                     const float* __restrict__ addend,
-                                                                     const float* __restrict__ mul2,
-                                                                     float* __restrict__ out, float* __restrict__ out2,
-                                                                     unsigned* __restrict__ absmax2_out, int64_t rows, int D) {
-    const int lane = threadIdx.x & 63;
-    const int64_t wave = ((int64_t)blockIdx.x * TPB + threadIdx.x) >> 6;
-    const int64_t nwaves = ((int64_t)gridDim.x * TPB) >> 6;
-    if constexpr (VEC) {
-        const bool on = lane * 4 < D;
-        f32x4 wv = {1.f, 1.f, 1.f, 1.f};
-        if (on && w) wv = *reinterpret_cast<const f32x4*>(w + lane * 4);
-        for (int64_t r = wave; r < rows; r += nwaves) {
-            const int64_t off = r * D + lane * 4;
-            f32x4 g = {0.f, 0.f, 0.f, 0.f}, ad = {0.f, 0.f, 0.f, 0.f}, m2 = {1.f, 1.f, 1.f, 1.f};
-            if (on) g = *reinterpret_cast<const f32x4*>(gy + off);
-            if (on && addend) ad = *reinterpret_cast<const f32x4*>(addend + off);
-            if (on && mul2) m2 = *reinterpret_cast<const f32x4*>(mul2 + off);
-            const float rs = rstd[r];
-            const f32x4 h = g * wv * rs;
-            const float mh = wave_sum((h[0] + h[1]) + (h[2] + h[3])) / (float)D;
-            const f32x4 o = h - mh + ad;
-            const f32x4 o2 = o * m2;
-            if (on && out) *reinterpret_cast<f32x4*>(out + off) = o;
-            if (on && out2) *reinterpret_cast<f32x4*>(out2 + off) = o2;
-            if (absmax2_out) {
-                const unsigned m = wave_max_u32(on ? absbits4(o2) : 0u);
-                if (lane == 0) absmax2_out[r] = m;
-            }
-        }
-    } else {
-        for (int64_t r = wave; r < rows; r += nwaves) {
-            const float* g = gy + r * D;
-            const float rs = rstd[r];
-            float s = 0.f;
-            for (int c = lane; c < D; c += 64) s += g[c] * (w ? w[c] : 1.f) * rs;
-            const float mh = wave_sum(s) / (float)D;
-            unsigned m = 0u;
-            for (int c = lane; c < D; c += 64) {
-                float o = g[c] * (w ? w[c] : 1.f) * rs - mh;
-                if (addend) o += addend[r * D + c];
-                if (out) out[r * D + c] = o;
-                const float o2 = mul2 ? o * mul2[r * D + c] : o;
-                if (out2) out2[r * D + c] = o2;
-                m = max(m, __float_as_uint(o2) & 0x7fffffffu);
-            }
-            if (absmax2_out) {
-                m = wave_max_u32(m);
-                if (lane == 0) absmax2_out[r] = m;
-            }
-        }
-    }
-}
 
 // ---- GELU with detachable gate: y = gate(x) * x, gate = 0.5 (1 + erf(x / sqrt 2)) ------------------------------
 __global__ __launch_bounds__(TPB) void gelu_gate_kernel(const float* __restrict__ x, float* __restrict__ y,
@@ -776,12 +549,6 @@ __global__ __launch_bounds__(TPB) void finalize_patches_kernel(const float* __re
     }
 }
 
-inline unsigned grid_rows(int64_t rows) {
-    int64_t b = (rows * 64 + TPB - 1) / TPB;
-    if (b < 1) b = 1;
-    if (b > 256 * 8) b = 256 * 8;
-    return (unsigned)b;
-}
 inline unsigned grid_elems(int64_t n) {
     int64_t b = (n + TPB - 1) / TPB;
     if (b < 1) b = 1;
@@ -789,138 +556,7 @@ inline unsigned grid_elems(int64_t n) {
     return (unsigned)b;
 }
 
-// ---- GroupNorm over NHWC tensors (DetachableGroupNorm2d, centered_norms.py:93-160): one workgroup per (image, group) ------
-// Group g owns the channels [g cg, (g + 1) cg) of every pixel.  Three passes over the group's HW x cg values (mean, centred
-// sum of squares, normalise): the group of one image is at most a few MB and stays in L2 between the passes.
-__device__ inline float block_sum(float v, float* red) {
-    v = wave_sum(v);
-    __syncthreads();                                   // red may still be read from the previous reduction
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float t = 0.f;
-    for (int k = 0; k < TPB / 64; ++k) t += red[k];
-    return t;
-}
-
-__global__ __launch_bounds__(TPB) void groupnorm_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
-                                                            const float* __restrict__ b, float* __restrict__ y,
-                                                            float* __restrict__ rstd_out, int HW, int C, int G, float eps) {
-    __shared__ float red[TPB / 64];
-    const int n = blockIdx.x / G, g = blockIdx.x - n * G;
-    const int cg = C / G;
-    const int64_t base = (int64_t)n * HW * C + g * cg;
-    const int64_t m = (int64_t)HW * cg;
-    float s = 0.f;
-    for (int64_t e = threadIdx.x; e < m; e += TPB) s += x[base + (e / cg) * C + e % cg];
-    const float mean = block_sum(s, red) / (float)m;
-    float v = 0.f;
-    for (int64_t e = threadIdx.x; e < m; e += TPB) { const float d = x[base + (e / cg) * C + e % cg] - mean; v = fmaf(d, d, v); }
-    const float var = block_sum(v, red) / (float)m;
-    const float sd = sqrtf(var + eps);
-    for (int64_t e = threadIdx.x; e < m; e += TPB) {
-        const int c = (int)(e % cg);
-        const int64_t i = base + (e / cg) * C + c;
-        float o = (x[i] - mean) / sd;
-        if (w) o *= w[g * cg + c];
-        if (b) o += b[g * cg + c];
-        y[i] = o;
-    }
-    if (rstd_out && threadIdx.x == 0) rstd_out[blockIdx.x] = 1.0f / sd;
-}
-
-// explanation mode (variance constant, mean differentiable):  gx = h - mean_group(h),  h = gy * w / std
-__global__ __launch_bounds__(TPB) void groupnorm_bwd_detached_kernel(const float* __restrict__ gy, const float* __restrict__ w,
-                                                                     const float* __restrict__ rstd, float* __restrict__ gx,
-                                                                     int HW, int C, int G) {
-    __shared__ float red[TPB / 64];
-    const int n = blockIdx.x / G, g = blockIdx.x - n * G;
-    const int cg = C / G;
-    const int64_t base = (int64_t)n * HW * C + g * cg;
-    const int64_t m = (int64_t)HW * cg;
-    const float rs = rstd[blockIdx.x];
-    float s = 0.f;
-    for (int64_t e = threadIdx.x; e < m; e += TPB) {
-        const int c = (int)(e % cg);
-        s += gy[base + (e / cg) * C + c] * (w ? w[g * cg + c] : 1.0f) * rs;
-    }
-    const float mh = block_sum(s, red) / (float)m;
-    for (int64_t e = threadIdx.x; e < m; e += TPB) {
-        const int c = (int)(e % cg);
-        const int64_t i = base + (e / cg) * C + c;
-        gx[i] = gy[i] * (w ? w[g * cg + c] : 1.0f) * rs - mh;
-    }
-}
-
-// GroupNorm, nothing detached (F.group_norm's gradient): per (image, group) with m values,  x_hat = (x - mean) rstd, h = gy w:
-//   gx = rstd (h - mean(h) - x_hat mean(h x_hat));  x_hat is written out for the weight gradient (a column reduction)
-__global__ __launch_bounds__(TPB) void groupnorm_bwd_full_kernel(const float* __restrict__ gy, const float* __restrict__ x,
-                                                                 const float* __restrict__ w, const float* __restrict__ rstd,
-                                                                 float* __restrict__ gx, float* __restrict__ xhat, int HW, int C, int G) {
-    __shared__ float red[TPB / 64];
-    const int n = blockIdx.x / G, g = blockIdx.x - n * G;
-    const int cg = C / G;
-    const int64_t base = (int64_t)n * HW * C + g * cg;
-    const int64_t m = (int64_t)HW * cg;
-    const float rs = rstd[blockIdx.x];
-    float s = 0.f;
-    for (int64_t e = threadIdx.x; e < m; e += TPB) s += x[base + (e / cg) * C + e % cg];
-    const float mean = block_sum(s, red) / (float)m;
-    float sh = 0.f, shx = 0.f;
-    for (int64_t e = threadIdx.x; e < m; e += TPB) {
-        const int c = (int)(e % cg);
-        const int64_t i = base + (e / cg) * C + c;
-        const float xh = (x[i] - mean) * rs;
-        const float h = gy[i] * (w ? w[g * cg + c] : 1.0f);
-        sh += h;
-        shx = fmaf(h, xh, shx);
-    }
-    const float mh = block_sum(sh, red) / (float)m;
-    const float mhx = block_sum(shx, red) / (float)m;
-    for (int64_t e = threadIdx.x; e < m; e += TPB) {
-        const int c = (int)(e % cg);
-        const int64_t i = base + (e / cg) * C + c;
-        const float xh = (x[i] - mean) * rs;
-        const float h = gy[i] * (w ? w[g * cg + c] : 1.0f);
-        gx[i] = rs * (h - mh - xh * mhx);
-        if (xhat) xhat[i] = xh;
-    }
-}
-
 // ---- training-mode backward of the token path (SURVEY.md section 8(f) N4 for the ViT family) ---------------------------------
-// LayerNorm, nothing detached: x_hat = (x - mean) rstd, h = gy w:  gx = rstd (h - mean(h) - x_hat mean(h x_hat)); x_hat is also
-// written out for the weight gradient (sum_rows gy x_hat, a column reduction).  One wavefront per row.
-__global__ __launch_bounds__(TPB) void layernorm_bwd_full_kernel(const float* __restrict__ gy, const float* __restrict__ x,
-                                                                 const float* __restrict__ w, const float* __restrict__ rstd,
-                                                                 const float* __restrict__ addend, float* __restrict__ gx,
-                                                                 float* __restrict__ xhat, int64_t rows, int D) {
-    const int lane = threadIdx.x & 63;
-    const int64_t wave = ((int64_t)blockIdx.x * TPB + threadIdx.x) >> 6;
-    const int64_t nwaves = ((int64_t)gridDim.x * TPB) >> 6;
-    for (int64_t r = wave; r < rows; r += nwaves) {
-        const float* xs = x + r * D;
-        const float* gs = gy + r * D;
-        float s = 0.f;
-        for (int c = lane; c < D; c += 64) s += xs[c];
-        const float mean = wave_sum(s) / (float)D;
-        const float rs = rstd[r];
-        float sh = 0.f, shx = 0.f;
-        for (int c = lane; c < D; c += 64) {
-            const float xh = (xs[c] - mean) * rs;
-            const float h = gs[c] * (w ? w[c] : 1.0f);
-            sh += h;
-            shx = fmaf(h, xh, shx);
-        }
-        const float mh = wave_sum(sh) / (float)D, mhx = wave_sum(shx) / (float)D;
-        for (int c = lane; c < D; c += 64) {
-            const float xh = (xs[c] - mean) * rs;
-            const float h = gs[c] * (w ? w[c] : 1.0f);
-            const float g = rs * (h - mh - xh * mhx);
-            gx[r * D + c] = addend ? g + addend[r * D + c] : g;        // (the residual stream's gradient joins here)
-            if (xhat) xhat[r * D + c] = xh;
-        }
-    }
-}
-
 // GELU, gate not detached: d/dx [x Phi(x)] = Phi(x) + x phi(x)
 __global__ __launch_bounds__(TPB) void gelu_bwd_full_kernel(const float* __restrict__ gy, const float* __restrict__ x,
                                                             float* __restrict__ gx, int64_t n) {
@@ -1217,58 +853,6 @@ __global__ __launch_bounds__(256) void attention_bwd_mfma_kernel(const float* __
 
 #define STREAM(s) reinterpret_cast<hipStream_t>(s)
 
-static bool ln_vec_ok(int D, std::initializer_list<const void*> ptrs) {
-    uintptr_t bits = 0;
-    for (const void* q : ptrs) bits |= reinterpret_cast<uintptr_t>(q);
-    return D % 4 == 0 && D <= 256 && (bits & 15) == 0;
-}
-
-extern "C" int bcos_layernorm_fwd(const float* x, const float* weight, const float* bias, float* y, float* rstd_out,
-                                  uint32_t* y_absmax, int64_t rows, int D, float eps, void* stream) {
-    if (!x || !y || rows <= 0 || D <= 0) return bcos_set_error(BCOS_E_INVAL, "bcos_layernorm_fwd: bad argument");
-    if (ln_vec_ok(D, {x, weight, bias, y}))
-        hipLaunchKernelGGL(layernorm_fwd_kernel<true>, dim3(grid_rows(rows)), dim3(TPB), 0, STREAM(stream), x, weight, bias, y,
-                           rstd_out, y_absmax, rows, D, eps);
-    else
-        hipLaunchKernelGGL(layernorm_fwd_kernel<false>, dim3(grid_rows(rows)), dim3(TPB), 0, STREAM(stream), x, weight, bias, y,
-                           rstd_out, y_absmax, rows, D, eps);
-    return check_launch("layernorm_fwd_kernel");
-}
-
-extern "C" int bcos_layernorm_stats(const float* x, const float* weight, const float* bias, float* rstd_out, float* zsumsq_out,
-                                    uint32_t* x_absmax, int64_t rows, int D, float eps, void* stream) {
-    if (!x || !rstd_out || rows <= 0 || D <= 0) return bcos_set_error(BCOS_E_INVAL, "bcos_layernorm_stats: bad argument");
-    if (ln_vec_ok(D, {x, weight, bias})) {
-        int64_t nb = (rows + 15) / 16;           // 16 rows per workgroup and pass
-        if (nb > 256 * 32) nb = 256 * 32;
-        const dim3 grid((unsigned)nb), block(TPB);
-        hipStream_t st = STREAM(stream);
-        switch ((D + 63) / 64) {
-            case 1: hipLaunchKernelGGL(layernorm_stats16_kernel<1>, grid, block, 0, st, x, weight, bias, rstd_out, zsumsq_out, x_absmax, rows, D, eps); break;
-            case 2: hipLaunchKernelGGL(layernorm_stats16_kernel<2>, grid, block, 0, st, x, weight, bias, rstd_out, zsumsq_out, x_absmax, rows, D, eps); break;
-            case 3: hipLaunchKernelGGL(layernorm_stats16_kernel<3>, grid, block, 0, st, x, weight, bias, rstd_out, zsumsq_out, x_absmax, rows, D, eps); break;
-            default: hipLaunchKernelGGL(layernorm_stats16_kernel<4>, grid, block, 0, st, x, weight, bias, rstd_out, zsumsq_out, x_absmax, rows, D, eps); break;
-        }
-    } else
-        hipLaunchKernelGGL(layernorm_stats_kernel, dim3(grid_rows(rows)), dim3(TPB), 0, STREAM(stream), x, weight, bias, rstd_out,
-                           zsumsq_out, x_absmax, rows, D, eps);
-    return check_launch("layernorm_stats_kernel");
-}
-
-extern "C" int bcos_layernorm_bwd_detached(const float* gy, const float* weight, const float* rstd, const float* addend,
-                                           const float* mul2, float* out, float* out2, uint32_t* out2_absmax, int64_t rows, int D,
-                                           void* stream) {
-    if (!gy || !rstd || (!out && !out2) || rows <= 0 || D <= 0 || (out2_absmax && !out2))
-        return bcos_set_error(BCOS_E_INVAL, "bcos_layernorm_bwd_detached: bad argument");
-    if (ln_vec_ok(D, {gy, weight, addend, mul2, out, out2}))
-        hipLaunchKernelGGL(layernorm_bwd_detached_kernel<true>, dim3(grid_rows(rows)), dim3(TPB), 0, STREAM(stream), gy, weight,
-                           rstd, addend, mul2, out, out2, out2_absmax, rows, D);
-    else
-        hipLaunchKernelGGL(layernorm_bwd_detached_kernel<false>, dim3(grid_rows(rows)), dim3(TPB), 0, STREAM(stream), gy, weight,
-                           rstd, addend, mul2, out, out2, out2_absmax, rows, D);
-    return check_launch("layernorm_bwd_detached_kernel");
-}
-
 extern "C" int bcos_gelu_gate(const float* x, float* y, float* gate_out, int64_t n, void* stream) {
     if (!x || !y || n <= 0) return bcos_set_error(BCOS_E_INVAL, "bcos_gelu_gate: bad argument");
     hipLaunchKernelGGL(gelu_gate_kernel, dim3(grid_elems(n)), dim3(TPB), 0, STREAM(stream), x, y, gate_out, n);
@@ -1354,39 +938,6 @@ extern "C" int bcos_finalize_explanation_patches(const float* gp, const float* x
     return check_launch("finalize_patches_kernel");
 }
 
-extern "C" int bcos_groupnorm_fwd(const float* x, const float* weight, const float* bias, float* y, float* rstd_out, int N, int HW,
-                                  int C, int G, float eps, void* stream) {
-    if (!x || !y || N <= 0 || HW <= 0 || C <= 0 || G <= 0 || C % G != 0)
-        return bcos_set_error(BCOS_E_INVAL, "bcos_groupnorm_fwd: bad argument (C must be divisible by the group count)");
-    if ((int64_t)N * G >= ((int64_t)1 << 31)) return bcos_set_error(BCOS_E_NOSUP, "bcos_groupnorm_fwd: too many groups");
-    hipLaunchKernelGGL(groupnorm_fwd_kernel, dim3((unsigned)(N * G)), dim3(TPB), 0, STREAM(stream), x, weight, bias, y, rstd_out, HW,
-                       C, G, eps);
-    return check_launch("groupnorm_fwd_kernel");
-}
-
-extern "C" int bcos_groupnorm_bwd_detached(const float* gy, const float* weight, const float* rstd, float* gx, int N, int HW, int C,
-                                           int G, void* stream) {
-    if (!gy || !rstd || !gx || N <= 0 || HW <= 0 || C <= 0 || G <= 0 || C % G != 0)
-        return bcos_set_error(BCOS_E_INVAL, "bcos_groupnorm_bwd_detached: bad argument");
-    if ((int64_t)N * G >= ((int64_t)1 << 31)) return bcos_set_error(BCOS_E_NOSUP, "bcos_groupnorm_bwd_detached: too many groups");
-    hipLaunchKernelGGL(groupnorm_bwd_detached_kernel, dim3((unsigned)(N * G)), dim3(TPB), 0, STREAM(stream), gy, weight, rstd, gx, HW,
-                       C, G);
-    return check_launch("groupnorm_bwd_detached_kernel");
-}
-
-extern "C" int bcos_layernorm_bwd_add(const float* gy, const float* x, const float* weight, const float* rstd, const float* addend,
-                                      float* gx, float* xhat_out, int64_t rows, int D, void* stream) {
-    if (!gy || !x || !rstd || !gx || rows <= 0 || D <= 0) return bcos_set_error(BCOS_E_INVAL, "bcos_layernorm_bwd: bad argument");
-    hipLaunchKernelGGL(layernorm_bwd_full_kernel, dim3(grid_rows(rows)), dim3(TPB), 0, STREAM(stream), gy, x, weight, rstd, addend, gx,
-                       xhat_out, rows, D);
-    return check_launch("layernorm_bwd_full_kernel");
-}
-
-extern "C" int bcos_layernorm_bwd(const float* gy, const float* x, const float* weight, const float* rstd, float* gx, float* xhat_out,
-                                  int64_t rows, int D, void* stream) {
-    return bcos_layernorm_bwd_add(gy, x, weight, rstd, nullptr, gx, xhat_out, rows, D, stream);
-}
-
 extern "C" int bcos_gelu_bwd(const float* gy, const float* x, float* gx, int64_t n, void* stream) {
     if (!gy || !x || !gx || n <= 0) return bcos_set_error(BCOS_E_INVAL, "bcos_gelu_bwd: bad argument");
     int64_t blocks = (n + TPB - 1) / TPB;
@@ -1419,14 +970,4 @@ extern "C" int bcos_attention_bwd(const float* qkv, const float* stats, const fl
     hipLaunchKernelGGL(attention_bwd_full_kernel, dim3((unsigned)(B * H)), dim3(256), bytes, STREAM(stream), qkv, stats, out, gout, gqkv,
                        B, T, H, scale);
     return check_launch("attention_bwd_full_kernel");
-}
-
-extern "C" int bcos_groupnorm_bwd(const float* gy, const float* x, const float* weight, const float* rstd, float* gx, float* xhat_out,
-                                  int N, int HW, int C, int G, void* stream) {
-    if (!gy || !x || !rstd || !gx || N <= 0 || HW <= 0 || C <= 0 || G <= 0 || C % G != 0)
-        return bcos_set_error(BCOS_E_INVAL, "bcos_groupnorm_bwd: bad argument");
-    if ((int64_t)N * G >= ((int64_t)1 << 31)) return bcos_set_error(BCOS_E_NOSUP, "bcos_groupnorm_bwd: too many groups");
-    hipLaunchKernelGGL(groupnorm_bwd_full_kernel, dim3((unsigned)(N * G)), dim3(TPB), 0, STREAM(stream), gy, x, weight, rstd, gx, xhat_out,
-                       HW, C, G);
-    return check_launch("groupnorm_bwd_full_kernel");
 }

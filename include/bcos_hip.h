@@ -861,7 +861,7 @@ int bcos_relu_bwd_colsums(const float* g, const float* act, const float* y, floa
 int bcos_channel_axpby(const float* a, const float* sa, const float* b, const float* mb, const float* sb, float* out,
                        int64_t rows, int C, void* stream);
 
-/* -- transformer pieces (bcos_vit.hip) ---------------------------------------------------- */
+/* -- transformer pieces (bcos_vit.hip; the LayerNorm / GroupNorm entry points: bcos_norms.hip) ---- */
 
 /* Accuracy, per element, of the LayerNorm / GroupNorm / GELU / un-patchify entry points of this section and of their training-mode
  * gradients further down (tests/token_cases.py, tests/test_token_kernels_gpu.py).  Against the same expressions in fp64 from the fp32
@@ -1410,7 +1410,7 @@ int bcos_dwconv7_wgrad(const float* gy, const float* mul, float gain, const floa
  * C % 4 != 0, or more than 2^31 - 1 bytes (C > 21396 at G = 256), which bcos_dwconv7_wgrad refuses as well. */
 int bcos_dwconv7_wgrad_workspace(int N, int H, int W, int C);
 
-/* -- uncentered position / group norms (csrc/bcos_unorm.hip; additive, ABI v12) ---------------------------------------------
+/* -- uncentered position / group norms (csrc/bcos_norms.hip; additive, ABI v12) ---------------------------------------------
  * The norms of the B-cos v2 norm ablations whose variance is centred while the value that is divided is NOT: over a set S of n values
  * (a row of x [rows, D] = the channels of a pixel of the NHWC image; an (image, group) of x [N, HW, C])
  *     m = mean_S x,   var = mean_S (x - m)^2,   r = 1 / sqrt(var + eps),   y = weight x r + bias        (weight / bias may be NULL)

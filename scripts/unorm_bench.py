@@ -1,4 +1,4 @@
-"""The uncentered position / group norm kernels (csrc/bcos_unorm.hip) and the B-cos ConvNeXt-T built on them, one JSON line (DESIGN:
+"""The uncentered position / group norm kernels (csrc/bcos_norms.hip, centered=False) and the B-cos ConvNeXt-T built on them, one JSON line (DESIGN:
 "Uncentered norms"; needs a HIP device):
 
   kernels   bcos_layernorm_unc_fwd (rstd kept), _bwd_detached and _bwd over the rows of the NHWC image at the four ConvNeXt-T stages, batch
@@ -90,15 +90,15 @@ def step_kernels(args):
         mk = lambda: torch.randn(rows, Cc, generator=g).to(DEV)      # noqa: E731
         x, gy, out = mk() + 0.5, mk(), mk()
         w = (torch.rand(Cc, generator=g) + 0.5).to(DEV)
-        _, rstd_u = ops.layernorm_unc_fwd(x, w, None, 1e-6, want_rstd=True)
+        _, rstd_u = ops.layernorm_fwd(x, w, None, 1e-6, want_rstd=True, centered=False)
         _, rstd_c = ops.layernorm_fwd(x, w, None, 1e-6, want_rstd=True)
         n = x.numel()
         launches = (
-            ("forward_keep_rstd", lambda: ops.layernorm_unc_fwd(x, w, None, 1e-6, want_rstd=True, out=out),
+            ("forward_keep_rstd", lambda: ops.layernorm_fwd(x, w, None, 1e-6, want_rstd=True, out=out, centered=False),
              lambda: ops.layernorm_fwd(x, w, None, 1e-6, want_rstd=True, out=out), 2 * n),
-            ("backward_detached", lambda: ops.layernorm_unc_bwd_detached(gy, w, rstd_u, out=out),
+            ("backward_detached", lambda: ops.layernorm_bwd_detached(gy, w, rstd_u, out=out, centered=False),
              lambda: ops.layernorm_bwd_detached(gy, w, rstd_c, out=out), 2 * n),
-            ("backward_full", lambda: ops.layernorm_unc_bwd(gy, x, w, rstd_u), lambda: ops.layernorm_bwd(gy, x, w, rstd_c), 3 * n))
+            ("backward_full", lambda: ops.layernorm_bwd(gy, x, w, rstd_u, centered=False), lambda: ops.layernorm_bwd(gy, x, w, rstd_c), 3 * n))
         shapes[f"rows {N}x{HW}x{HW}, D {Cc}"] = dict(_time_group(launches, args.iters), kernel_form="float4" if Cc <= 256 else "strided")
         del x, gy, out
         torch.cuda.empty_cache()
@@ -107,13 +107,13 @@ def step_kernels(args):
     mk = lambda: torch.randn(N, HW, HW, Cc, generator=g).to(DEV)      # noqa: E731
     x, gy = mk() + 0.5, mk()
     w, b = (torch.rand(Cc, generator=g) + 0.5).to(DEV), torch.randn(Cc, generator=g).to(DEV)
-    _, rstd_u = ops.groupnorm_unc_fwd(x, G, w, b, 1e-5, want_rstd=True)
+    _, rstd_u = ops.groupnorm_fwd(x, G, w, b, 1e-5, want_rstd=True, centered=False)
     _, rstd_c = ops.groupnorm_fwd(x, G, w, b, 1e-5, want_rstd=True)
     n = x.numel()
     launches = (
-        ("forward_keep_rstd", lambda: ops.groupnorm_unc_fwd(x, G, w, b, 1e-5, want_rstd=True), lambda: ops.groupnorm_fwd(x, G, w, b, 1e-5, want_rstd=True), 2 * n),
-        ("backward_detached", lambda: ops.groupnorm_unc_bwd_detached(gy, G, w, rstd_u), lambda: ops.groupnorm_bwd_detached(gy, G, w, rstd_c), 2 * n),
-        ("backward_full", lambda: ops.groupnorm_unc_bwd(gy, x, G, w, rstd_u), lambda: ops.groupnorm_bwd(gy, x, G, w, rstd_c), 3 * n))
+        ("forward_keep_rstd", lambda: ops.groupnorm_fwd(x, G, w, b, 1e-5, want_rstd=True, centered=False), lambda: ops.groupnorm_fwd(x, G, w, b, 1e-5, want_rstd=True), 2 * n),
+        ("backward_detached", lambda: ops.groupnorm_bwd_detached(gy, G, w, rstd_u, centered=False), lambda: ops.groupnorm_bwd_detached(gy, G, w, rstd_c), 2 * n),
+        ("backward_full", lambda: ops.groupnorm_bwd(gy, x, G, w, rstd_u, centered=False), lambda: ops.groupnorm_bwd(gy, x, G, w, rstd_c), 3 * n))
     shapes[f"group {N}x{HW}x{HW}x{Cc}, G {G}"] = dict(_time_group(launches, args.iters), kernel_form="one workgroup per (image, group)")
     return dict(batch=N, shapes=shapes, iters=args.iters, device=torch.cuda.get_device_name(0))
 

@@ -393,23 +393,29 @@ def weight_rownorm_bwd(w2d, g2d, gain=None, want_gw=True, want_ggain=False):
     return gw, (dot.view(-1) if want_ggain else None)
 
 
-def layernorm_bwd(gy2d, x2d, weight, rstd, want_xhat=False, addend=None):
-    x = x2d.double()
-    xhat = (x - x.mean(1, keepdim=True)) * rstd.double().view(-1, 1)
+def layernorm_bwd(gy2d, x2d, weight, rstd, want_xhat=False, addend=None, centered=True):
+    x, rs = x2d.double(), rstd.double().view(-1, 1)
+    xhat = (x - x.mean(1, keepdim=True)) * rs
     h = gy2d.double() * (weight.double() if weight is not None else 1.0)
-    gx = rstd.double().view(-1, 1) * (h - h.mean(1, keepdim=True) - xhat * (h * xhat).mean(1, keepdim=True))
+    if centered:
+        gx = rs * (h - h.mean(1, keepdim=True) - xhat * (h * xhat).mean(1, keepdim=True))
+    else:               # gx = r h - r^3 (x - mean) (sum h x) / n; the second result is x r
+        gx, xhat = rs * h - rs ** 2 * xhat * (h * x).mean(1, keepdim=True), x * rs
     if addend is not None:
         gx = gx.float().double() + addend.double()          # (the kernel rounds the LayerNorm term to fp32 first)
     return gx.float(), (xhat.float() if want_xhat else None)
 
 
-def groupnorm_bwd(gy_nhwc, x_nhwc, groups, weight, rstd, want_xhat=False):
+def groupnorm_bwd(gy_nhwc, x_nhwc, groups, weight, rstd, want_xhat=False, centered=True):
     N, H, W, Cc = gy_nhwc.shape
     xg = x_nhwc.reshape(N, H * W, groups, Cc // groups).double()
     rs = rstd.double().view(N, 1, groups, 1)
     xhat = (xg - xg.mean(dim=(1, 3), keepdim=True)) * rs
     h = (gy_nhwc.double() * (weight.double() if weight is not None else 1.0)).reshape(N, H * W, groups, Cc // groups)
-    gx = rs * (h - h.mean(dim=(1, 3), keepdim=True) - xhat * (h * xhat).mean(dim=(1, 3), keepdim=True))
+    if centered:
+        gx = rs * (h - h.mean(dim=(1, 3), keepdim=True) - xhat * (h * xhat).mean(dim=(1, 3), keepdim=True))
+    else:               # gx = r h - r^3 (x - mean) (sum h x) / n; the second result is x r
+        gx, xhat = rs * h - rs ** 2 * xhat * (h * xg).mean(dim=(1, 3), keepdim=True), xg * rs
     return gx.reshape(N, H, W, Cc).float(), (xhat.reshape(N, H, W, Cc).float() if want_xhat else None)
 
 
@@ -435,13 +441,13 @@ def attention_bwd(qkv, stats, out, gout, heads, scale):
     return torch.cat([pack(gq), pack(gk), pack(gv)], dim=-1).float()
 
 
-def groupnorm_fwd(x_nhwc, groups, weight, bias, eps, want_rstd=False):
+def groupnorm_fwd(x_nhwc, groups, weight, bias, eps, want_rstd=False, centered=True):
     N, H, W, Cc = x_nhwc.shape
     xg = x_nhwc.reshape(N, H * W, groups, Cc // groups).double()
     mean = xg.mean(dim=(1, 3), keepdim=True)
     var = ((xg - mean) ** 2).mean(dim=(1, 3), keepdim=True)
     rstd = 1.0 / (var + eps).sqrt()
-    y = ((xg - mean) * rstd).reshape(N, H, W, Cc)
+    y = ((xg - mean if centered else xg) * rstd).reshape(N, H, W, Cc)
     if weight is not None:
         y = y * weight.double()
     if bias is not None:
@@ -449,11 +455,11 @@ def groupnorm_fwd(x_nhwc, groups, weight, bias, eps, want_rstd=False):
     return y.float(), (rstd.reshape(-1).float() if want_rstd else None)
 
 
-def groupnorm_bwd_detached(gy_nhwc, groups, weight, rstd):
+def groupnorm_bwd_detached(gy_nhwc, groups, weight, rstd, centered=True):
     N, H, W, Cc = gy_nhwc.shape
     h = gy_nhwc.double() * (weight.double() if weight is not None else 1.0)
     h = h.reshape(N, H * W, groups, Cc // groups) * rstd.double().view(N, 1, groups, 1)
-    return (h - h.mean(dim=(1, 3), keepdim=True)).reshape(N, H, W, Cc).float()
+    return (h - h.mean(dim=(1, 3), keepdim=True) if centered else h).reshape(N, H, W, Cc).float()
 
 
 def maxout_scatter(g2d, argmax2d, max_out):
@@ -558,10 +564,10 @@ def maxout_scale(lin2d, norm, Cout, max_out, b, groups=1, want_scale=False, want
     return y, (s if want_scale else None), (arg.to(torch.int32) if want_argmax else None)
 
 
-def layernorm_fwd(x2d, weight, bias, eps, want_rstd=False, out=None, want_absmax=False):
+def layernorm_fwd(x2d, weight, bias, eps, want_rstd=False, out=None, want_absmax=False, centered=True):
     var, mean = torch.var_mean(x2d.double(), dim=-1, unbiased=False, keepdim=True)
     sd = (var + eps).sqrt()
-    y = (x2d.double() - mean) / sd
+    y = (x2d.double() - mean if centered else x2d.double()) / sd
     if weight is not None:
         y = y * weight.double()
     if bias is not None:
@@ -574,9 +580,10 @@ def layernorm_stats(x2d, weight, bias, eps, want_zsumsq=False, want_absmax=False
     return rstd, ((y.double() ** 2).sum(-1).float() if want_zsumsq else None)
 
 
-def layernorm_bwd_detached(gy2d, weight, rstd, addend=None, mul2=None, want_out=True, want_out2=False, out=None, want_absmax2=False):
+def layernorm_bwd_detached(gy2d, weight, rstd, addend=None, mul2=None, want_out=True, want_out2=False, out=None, want_absmax2=False,
+                           centered=True):
     h = gy2d.double() * (weight.double() if weight is not None else 1.0) * rstd.double().view(-1, 1)
-    g = h - h.mean(-1, keepdim=True)
+    g = h - h.mean(-1, keepdim=True) if centered else h
     if addend is not None:
         g = g + addend.double()
     o2 = (g * mul2.double() if mul2 is not None else g).float() if want_out2 else None

@@ -105,13 +105,15 @@ def test_header_sources_and_prototypes():
         assert name in lib.SIGNATURES, name
         decl = re.search(r"^int " + name + r"\((.*?)\);", header, re.M | re.S).group(1)
         assert len(decl.split(",")) == len(lib.SIGNATURES[name][1]), name              # one ctypes type per declared argument
-    assert "bcos_unorm.hip" in lib.SOURCES and (lib.CSRC / "bcos_unorm.hip").exists()
+    assert "bcos_norms.hip" in lib.SOURCES and (lib.CSRC / "bcos_norms.hip").exists()
     for ref in ("posnorm_uncentered.py:39-58", "groupnorm_uncentered.py:21-61"):       # the declarations carry the reference's file:line
         assert ref in header, ref
     assert lib.ABI_VERSION == 12 and re.search(r"#define\s+BCOS_ABI_VERSION\s+12\b", header)
     from bcos_hip import ops
-    for name in ENTRY_POINTS:
-        assert callable(getattr(ops, name[len("bcos_"):])), name
+    for name in ENTRY_POINTS:               # reached through the wrapper of the centred operation, `centered=False`
+        wrapper = getattr(ops, name[len("bcos_"):].replace("_unc_", "_"))
+        assert callable(wrapper) and inspect.signature(wrapper).parameters["centered"].default is True, name
+        assert not hasattr(ops, name[len("bcos_"):]), name
 
 
 def test_argument_errors_return_inval_without_a_device(hip_lib):

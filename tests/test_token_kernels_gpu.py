@@ -1,17 +1,18 @@
-"""`-m gpu`: every case of tests/token_cases.py through the token-path entry points of csrc/bcos_vit.hip, launched through the C ABI (raw
-pointers: the misaligned cases are views that bcos_hip.ops would not pass) and judged PER ELEMENT against the same operation in fp64
-(the reference, the bound forms and their constants: tests/token_cases.py; stated in include/bcos_hip.h).
+"""`-m gpu`: every case of tests/token_cases.py through the token-path entry points of csrc/bcos_vit.hip and the centred norms of
+csrc/bcos_norms.hip, launched through the C ABI (raw pointers: the misaligned cases are views that bcos_hip.ops would not pass) and
+judged PER ELEMENT against the same operation in fp64 (the reference, the bound forms and their constants:
+tests/token_cases.py; stated in include/bcos_hip.h).
 
 Which case reaches which kernel:
-  layernorm_fwd_kernel<VEC>, layernorm_bwd_detached_kernel<VEC>   ln-* with D in {4, 64, 68, 192, 252, 256} (D = 8 for the second pass)
-  layernorm_fwd_kernel<!VEC>, layernorm_bwd_detached_kernel<!VEC> ln-* with D in {1, 3, 50, 65, 260, 384, 768, 1000} (D = 5 for the second
+  norm_rows_fwd / _bwd_detached_kernel<VEC, CENTERED>             ln-* with D in {4, 64, 68, 192, 252, 256} (D = 8 for the second pass)
+  norm_rows_fwd / _bwd_detached_kernel<!VEC, CENTERED>            ln-* with D in {1, 3, 50, 65, 260, 384, 768, 1000} (D = 5 for the second
                                                                   pass), and every D % 4 == 0 case again with x, y or w one float off a
                                                                   16-byte boundary (test_misaligned_operands_take_the_strided_kernels)
   layernorm_stats16_kernel<1> .. <4>                              `stats` of D = 4 and 64 / 68 / 192 / 252 and 256, each with rows 1 and 5;
                                                                   the second pass (131072 rows) at ln-*-r131093d4 and -r131093d68
   layernorm_stats_kernel                                          `stats` of the strided widths; second pass at ln-offset-r8229d5
-  layernorm_bwd_full_kernel                                       `bwd` of every ln-* case (bcos_layernorm_bwd and bcos_layernorm_bwd_add)
-  groupnorm_fwd / _bwd_detached / _bwd_full_kernel                gn-*: m = HW C / G of 1, 2, 255, 256, 257 and beyond; cg of 1, 2, 3, 4, 6, 64; G = 1
+  norm_rows_bwd_full_kernel<!VEC, CENTERED>                       `bwd` of every ln-* case (bcos_layernorm_bwd and bcos_layernorm_bwd_add)
+  norm_group_fwd / _bwd_detached / _bwd_full_kernel<CENTERED>     gn-*: m = HW C / G of 1, 2, 255, 256, 257 and beyond; cg of 1, 2, 3, 4, 6, 64; G = 1
   gelu_gate_kernel, gelu_bwd_full_kernel                          gelu-gate-*, gelu-bwd-*; the long ones run 77 elements of a second pass
   add_rows_bcast_kernel                                           add-*; add-b512t1d4104 goes past the grid cap
   finalize_patches_kernel, 16-byte record loads                   fin-*c8-* (fin-n65h256w256p16c8-inv1 goes past the grid cap)
@@ -273,7 +274,7 @@ def test_layernorm_case_against_fp64_per_element(blib, case, op):
 
 def test_misaligned_operands_take_the_strided_kernels(blib):
     """every D % 4 == 0 case of up to 333 rows again with ONE operand a view one float into its buffer -- x (gy), then y (out), then w:
-    ln_vec_ok sends the call to the strided kernels (a 16-byte access there would fault or read the neighbour), which meet the same bounds"""
+    vec_ok sends the call to the strided kernels (a 16-byte access there would fault or read the neighbour), which meet the same bounds"""
     lib = blib.load()
     n = 0
     for case in tc.LN_CASES:

@@ -1,6 +1,6 @@
 """The reference and the bounds of tests/unorm_cases.py, without a device:
 
-  * the case table is the one the constants were measured on, and it reaches every code path of csrc/bcos_unorm.hip;
+  * the case table is the one the constants were measured on, and it reaches every uncentered code path of csrc/bcos_norms.hip;
   * the constants are what the module says they are: for every case the plain fp32 PyTorch evaluation of the documented expressions
     stays within K / 4 of each bound form, and the worst use over the table is the measurement the constants were set from;
   * the bounds are sharp enough to matter: three deliberate mistakes, each applied to the fp32 evaluation, break their bound on a named

@@ -1,12 +1,12 @@
-"""`-m gpu`: every case of tests/unorm_cases.py through the six entry points of csrc/bcos_unorm.hip, launched through the C ABI (raw
+"""`-m gpu`: every case of tests/unorm_cases.py through the six uncentered entry points of csrc/bcos_norms.hip, launched through the C ABI (raw
 pointers: the misaligned cases are views that bcos_hip.ops would not pass) and judged PER ELEMENT against the same operation in fp64
 (the reference, the bound forms and their constants: tests/unorm_cases.py; stated in include/bcos_hip.h).
 
 Which case reaches which kernel:
-  unorm_rows_*_kernel<VEC>      row-* with D in {4, 64, 68, 96, 252, 256} (D = 8 for the second pass of the grid-stride loop)
-  unorm_rows_*_kernel<!VEC>     row-* with D in {1, 3, 50, 65, 260, 1000} (D = 5 for the second pass) and the `-mis` cases: D = 68 and
-                                256 with x / gy / y / out one float off a 16-byte boundary
-  unorm_group_*_kernel          grp-*: n = HW C / G of 1, 2, 255, 256, 257 .. 18816; cg of 1, 2, 3, 4, 6, 64; G = 1 .. C
+  norm_rows_*_kernel<VEC, !CENTERED>    row-* with D in {4, 64, 68, 96, 252, 256} (D = 8 for the second pass of the grid-stride loop)
+  norm_rows_*_kernel<!VEC, !CENTERED>   row-* with D in {1, 3, 50, 65, 260, 1000} (D = 5 for the second pass) and the `-mis` cases: D = 68 and
+                                        256 with x / gy / y / out one float off a 16-byte boundary
+  norm_group_*_kernel<!CENTERED>        grp-*: n = HW C / G of 1, 2, 255, 256, 257 .. 18816; cg of 1, 2, 3, 4, 6, 64; G = 1 .. C
 
 For a case and an entry point:
   * every element of every output is held to its bound; a failure names the form, the worst element and its use of the form in units of u;

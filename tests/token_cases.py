@@ -1,5 +1,5 @@
-"""The case tables of the token-path entry points of csrc/bcos_vit.hip (include/bcos_hip.h: bcos_layernorm_fwd / _stats / _bwd_detached /
-_bwd / _bwd_add, bcos_groupnorm_fwd / _bwd_detached / _bwd, bcos_gelu_gate / bcos_gelu_bwd, bcos_add_rows_bcast,
+"""The case tables of the token-path entry points of csrc/bcos_vit.hip and csrc/bcos_norms.hip (include/bcos_hip.h: bcos_layernorm_fwd /
+_stats / _bwd_detached / _bwd / _bwd_add, bcos_groupnorm_fwd / _bwd_detached / _bwd, bcos_gelu_gate / bcos_gelu_bwd, bcos_add_rows_bcast,
 bcos_finalize_explanation_patches), the fp64 reference of what they compute and the PER-ELEMENT bounds every output is held to.
 
 Reference: the documented expressions in fp64 from the fp32 inputs promoted (eps is the fp32 value the entry point receives, promoted).
@@ -150,7 +150,7 @@ class FIN:
         return f"fin-n{self.N}h{self.H}w{self.W}p{self.ps}c{self.Cpad}-inv{self.add_inverse}" + ("-mis" if self.gp_offset else "")
 
 
-# widths of the one-float4-per-lane kernels and of the strided loop (ln_vec_ok: D % 4 == 0 and D <= 256), NV of layernorm_stats16_kernel
+# widths of the one-float4-per-lane kernels and of the strided loop (vec_ok: D % 4 == 0 and D <= 256), NV of layernorm_stats16_kernel
 VEC_WIDTHS = (4, 64, 68, 192, 252, 256)
 STRIDED_WIDTHS = (1, 3, 50, 65, 260, 384, 768, 1000)
 FIRST_PASS_ROWS = 8192               # grid_rows: 2048 workgroups of four rows

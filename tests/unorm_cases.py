@@ -1,4 +1,4 @@
-"""The case table of the uncentered-norm entry points of csrc/bcos_unorm.hip (include/bcos_hip.h: bcos_layernorm_unc_fwd / _bwd_detached /
+"""The case table of the uncentered-norm entry points of csrc/bcos_norms.hip (include/bcos_hip.h: bcos_layernorm_unc_fwd / _bwd_detached /
 _bwd, bcos_groupnorm_unc_fwd / _bwd_detached / _bwd), the fp64 reference of what they compute and the PER-ELEMENT bounds every output is
 held to.  The manner is that of tests/token_cases.py, whose input families, affine vectors, (image, group) <-> row mapping and `use` this
 module shares.
